@@ -2,6 +2,10 @@
 """bench.py -- CAF frames/s of the range-Doppler hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4|cfg5|cfg3|cfg1|cfg2p2] [--frames B]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps, writes its outputs if --dump-outputs is given and prints the line; the
+extra objects listed at the end (and the configs-3/5 legs) are measured only with --full.
 
 A *step* is one pass of the hot path (main.py:169-194 semantics) over one batch of B frames per GPU
 of synthetic two-channel complex64 IQ already resident in HBM: LS_Filter_Multiple on the B hop chunks
@@ -25,7 +29,13 @@ Workloads (BASELINE.json configs):
 `--gpus N` with N > 1 and no launcher around it starts the N ranks itself (torch.distributed.run on 127.0.0.1) and refuses
 to run when the host has fewer GPUs; under a launcher it checks WORLD_SIZE against N.
 
-One JSON line on rank 0 (contract in the task statement) with these extra objects:
+--dump-outputs DIR (rank 0): after the timed steps, a fixed, seeded sample of the maps the last step returned -- the same
+cells of every illuminator's maps -- as DIR/maps.npy (float32 [illuminators][cells][re, im]) and DIR/sample_index.npy
+(float64 flat indices into one illuminator's [frames][Doppler][range] maps), under 48 MB in all.  The inputs are seeded, so
+two builds given the same arguments can be compared output for output.  (--workload prconfig: maps.npy and cfar.npy.)
+
+One JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, the configuration); with --full, these
+extra objects:
   roofline     : the dominant kernel's rate on the HBM bytes it MOVED (2 x FETCH_SIZE + WRITE_SIZE of this run's own
                  rocprofv3 --pmc child passes; the committed per-unit figures or the analytic bytes when they cannot run --
                  `frac_basis` says which) over its average launch time (HIP events on the launch stream, kernel alone),
@@ -132,6 +142,28 @@ def synth_padded(torch, nchunks, C, fs, R, seed, device, add_to=None):
         srv_pad[lo:lo + a.shape[0]] += s
         del a, s
     return ref_pad, srv_pad
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: sampled values + their indices
+DUMP_SEED = 20261015
+
+
+def dump_outputs(torch, out_dir, outputs, nframes):
+    """--dump-outputs: the same seeded sample of cells of every output tensor's first ``nframes`` frames, written as
+    <name>.npy (float32, [channels][cells] or [channels][cells][re, im] for complex outputs) + sample_index.npy (float64
+    flat indices into one channel's [frames][...] array).  outputs: {name: [device tensor per channel]}."""
+    os.makedirs(out_dir, exist_ok=True)
+    first = next(iter(outputs.values()))[0]
+    total = nframes * int(np.prod(first.shape[1:]))
+    per_cell = 8 + sum(len(ts) * (8 if ts[0].is_complex() else 4) for ts in outputs.values())
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, min(total, DUMP_BYTES // per_cell), replace=False))
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    idx_d = torch.from_numpy(idx).to(first.device)
+    for name, ts in outputs.items():
+        vals = torch.stack([t[:nframes].reshape(-1)[idx_d] for t in ts])
+        if vals.is_complex():
+            vals = torch.view_as_real(vals)
+        np.save(os.path.join(out_dir, name + ".npy"), vals.cpu().numpy().astype(np.float32))
 
 
 # ---- CPU baseline: the reference's NumPy/SciPy path on this box's host cores ------------------------
@@ -460,7 +492,7 @@ def secondary_leg(wl, steps=None, warmup=1, timeout=420):
     t0 = time.perf_counter()
     try:
         # steps: None = the workload's own sizing (>= 5 s of timed steps: 3-4 steps of config 3, ~1000 of config 5)
-        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", wl, "--warmup", str(warmup),
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", wl, "--warmup", str(warmup), "--full",
                "--no-cpu", "--traffic", "file", "--secondary", "none", "--in-step", "none"] + ([] if steps is None else ["--steps", str(steps)])
         r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=timeout)
         line = None
@@ -730,7 +762,7 @@ def prconfig_main(args):
         step_resident()
     torch.cuda.synchronize()
     res_err = float((maps_d.cpu() - maps_h).abs().max()) / float(maps_h.abs().max())   # against the pipelined step's maps
-    rsteps = max(steps, int(np.ceil(2.0 / max(dt_h2h / steps * 0.35, 1e-3))))           # about two seconds of timed work
+    rsteps = args.steps or max(steps, int(np.ceil(2.0 / max(dt_h2h / steps * 0.35, 1e-3))))   # default: ~2 s of timed work
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(rsteps):
@@ -738,6 +770,8 @@ def prconfig_main(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = nchunks * rsteps / dt
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, {"maps": [maps_d], "cfar": [cfar_d]}, nchunks)
     e = [ev() for _ in range(4)]
     e[0].record()
     be.front_end2(raw_ref_d, raw_srv_d, *fe_args, max_blocks=nbat, out_ref=ref_pad[lo:lo + nchunks * C],
@@ -858,7 +892,8 @@ def prconfig_main(args):
 
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (RANK / WORLD_SIZE unset): start the N ranks here --
-    re-exec under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1 -- so that the line can never
+    a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1, whose exit status this process
+    returns (it has already asked the runtime how many GPUs there are, so it is not replaced) -- so that the line can never
     claim fewer GPUs than were asked for (it used to benchmark ONE GPU and print n_gpus 1).  Fails loudly when
     the host exposes fewer than N GPUs, or when a launcher's WORLD_SIZE disagrees with --gpus."""
     if args.gpus < 1:
@@ -887,7 +922,8 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     print(f"[bench] --gpus {args.gpus} without a launcher: starting {args.gpus} ranks: {' '.join(cmd[1:8])} ...", file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def main():
@@ -957,6 +993,13 @@ def main():
     ap.add_argument("--dump", default=None, metavar="NPZ",
                     help="single GPU: save the maps of the last timed step's first, second, middle and last frame "
                          "(+ every frame's sum) so a test can hold the benchmarked path against an independent pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel timings, roofline and traffic (with "
+                         "their rocprofv3 child passes), the CPU baseline, the FM suppression figure and the configs-3/5 legs "
+                         "(--traffic, --in-step, --secondary, --no-cpu and --cpu-workers tune these).  --workload prconfig "
+                         "reports its side figures either way")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of what the last step computed as DIR/*.npy")
     args = ap.parse_args()
     self_launch(args)
     if args.markers:
@@ -966,10 +1009,10 @@ def main():
         return prconfig_main(args)
 
     # BASELINE configs 3 and 5, a few steps each, in child processes BEFORE this process touches the GPU (each leg has the
-    # whole 288 GB to itself; config 3 keeps 180 GB resident): the driver's one default invocation then carries driver-timed
-    # numbers for them too
+    # whole 288 GB to itself; config 3 keeps 180 GB resident): one --full invocation then carries numbers for them too
+    # 
     secondary = None
-    sec = args.secondary
+    sec = args.secondary if args.full else "none"
     if sec == "auto":
         sec = "cfg3,cfg5" if (args.workload == "cfg2" and args.gpus == 1 and not args.no_cpu and not args.no_clutter
                               and args.frames is None and "RANK" not in os.environ) else "none"
@@ -1274,6 +1317,9 @@ def main():
         rccl_seen = [[int(t[0].item()), int(t[1].item())] for t in every_info]
         rccl_nranks = rccl_seen[0][0] if comm is not None else None
         gathered_bytes = [float(t[2].item()) for t in every_info]
+    if args.dump_outputs and rank == 0 and nframes:
+        # this rank's maps of the last timed step, one tensor per illuminator it owns (the fence above waited for them)
+        dump_outputs(torch, args.dump_outputs, {"maps": outs[(stepno[0] - 1) % nsets]}, nframes)
     if args.dump and world == 1 and nframes:
         last = outs[(stepno[0] - 1) % nsets]
         pick = sorted({0, min(1, nframes - 1), nframes // 2, nframes - 1})
@@ -1302,13 +1348,55 @@ def main():
             np.savez(args.dump, world=world, m=m, first=f0, gathered_block=recv[last_gather["k"]][:m * world].cpu().numpy(),
                      own_frames=outs[(stepno[0] - 1) % nsets][0][f0:f0 + m].cpu().numpy())
 
-    # ---- per-kernel timing with HIP events on the launch stream (rank 0) --------------------
+    # ---- the line: what the headline figure needs (rank 0) ----------------------------------------
     result = None
     if rank == 0 and args.no_kernel_timing:
         result = {"metric": f"CAF frames/sec ({wl}; child pass of a counter / trace collection)", "value": value, "unit": "frames/s",
                   "n_gpus": world, "steps": steps, "warmup": max(args.warmup, 1), "ms_per_step": dt / steps * 1e3,
                   "config": {"workload": wl, "frames_per_gpu_per_step": nframes}}
     elif rank == 0:
+        m, dp = be.caf.method, be.caf.doppler
+        if strong:
+            par = (f"{frames_per_step_total} frames of one stream sharded contiguously x{world} (strong), "
+                   f"one gather of the maps per pass ({gather_mode})") if world > 1 else "single GPU, whole stream"
+        elif nill > 1:
+            par = (f"{nill} illuminators sharded {ill_ways}-way x {groups} frame group(s), surfaces stay on their GPU"
+                   if world > 1 else f"single GPU, {nill} illuminators")
+        else:
+            par = f"frame-sharded x{world}, gather of maps to rank 0 per {gsize} frames ({gather_mode})" if world > 1 \
+                else "single GPU"
+        result = {
+            "metric": "CAF frames/sec (1s CPI @ 2.4 MS/s, 256 range x 512 Doppler); HBM GB/s %peak"
+                      if wl in ("cfg2", "cfg4") else f"CAF frames/sec ({wl})",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": steps,
+            "warmup": max(args.warmup, 1), "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
+            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"{wl}: Fs={fs:g} N={n} R={R} F={F} clutter="
+                                   f"{clutter or 'none'}{' x5 Doppler bins, T=%d' % (R + 10) if clutter == 'ls' else ''}, "
+                                   + (f"{frames_per_step_total}-frame stream (600 s), " if strong else
+                                      f"{B} overlapped frames/GPU/step, ")
+                                   + f"sub-batches of {batch} (hop N/2), Kaiser(5) window"
+                                   + (f", {nill} illuminators / frame" if nill > 1 else ""),
+                       "frames_per_gpu_per_step": nframes, "frames_per_step_total": frames_per_step_total,
+                       "arithmetic": "complex64 streams, f32 FFT butterflies, f64 Levinson-Durbin / tap solves",
+                       "caf_method": {1: "direct", 2: "fft"}.get(m, m),
+                       "doppler_method": {1: "rocfft"}.get(dp, dp),
+                       "parallelism": par},
+            "timed_seconds": dt,
+            # a rehearsal of the multi-rank control flow (gloo, ranks sharing a GPU): NOT a scaling number
+            "rehearsal": (f"{args.dist_backend} backend, {world} ranks on {torch.cuda.device_count()} GPU(s): control flow only, "
+                          f"not a number of record") if rehearsal else None,
+            # which code moved the maps (prc = prc_gather_frames: RCCL send/recv group through the C ABI; torch =
+            # torch.distributed.gather; none = single GPU or surfaces stay put) and every rank's own clock
+            "gather_path": gather_mode, "rccl_version": _lib.rccl_version() if gather_mode == "prc" else None,
+            # what RCCL itself reports for the communicator behind prc_gather_frames (ncclCommCount / ncclCommUserRank on
+            # every rank, all-gathered) and the bytes of maps every rank handed to the gather per step
+            "rccl_nranks": rccl_nranks, "rccl_ranks_seen": rccl_seen, "gathered_bytes_per_rank_per_step": gathered_bytes,
+            "rank_ms_per_step": [t / steps * 1e3 for t in rank_seconds],
+        }
+    # ---- --full: per-kernel timing with HIP events on the launch stream, traffic, CPU baseline (rank 0) ----
+    if result is not None and args.full and not args.no_kernel_timing:
         reps = 5
         nb = min(batch, nframes)
         ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -1450,45 +1538,7 @@ def main():
             per_frame_bytes = nill * 8.0 * n + 8.0 * n + 4.0 * n + nill * 8.0 * F * (R + 1)
         else:
             per_frame_bytes = caf_bytes + (200.0 * C if clutter == "ls" else (24.0 * C if clutter == "nlms" else 0.0))
-        m, dp = be.caf.method, be.caf.doppler
-        if strong:
-            par = (f"{frames_per_step_total} frames of one stream sharded contiguously x{world} (strong), "
-                   f"one gather of the maps per pass ({gather_mode})") if world > 1 else "single GPU, whole stream"
-        elif nill > 1:
-            par = (f"{nill} illuminators sharded {ill_ways}-way x {groups} frame group(s), surfaces stay on their GPU"
-                   if world > 1 else f"single GPU, {nill} illuminators")
-        else:
-            par = f"frame-sharded x{world}, gather of maps to rank 0 per {gsize} frames ({gather_mode})" if world > 1 \
-                else "single GPU"
-        result = {
-            "metric": "CAF frames/sec (1s CPI @ 2.4 MS/s, 256 range x 512 Doppler); HBM GB/s %peak"
-                      if wl in ("cfg2", "cfg4") else f"CAF frames/sec ({wl})",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": steps,
-            "warmup": max(args.warmup, 1), "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
-            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"{wl}: Fs={fs:g} N={n} R={R} F={F} clutter="
-                                   f"{clutter or 'none'}{' x5 Doppler bins, T=%d' % (R + 10) if clutter == 'ls' else ''}, "
-                                   + (f"{frames_per_step_total}-frame stream (600 s), " if strong else
-                                      f"{B} overlapped frames/GPU/step, ")
-                                   + f"sub-batches of {batch} (hop N/2), Kaiser(5) window"
-                                   + (f", {nill} illuminators / frame" if nill > 1 else ""),
-                       "frames_per_gpu_per_step": nframes, "frames_per_step_total": frames_per_step_total,
-                       "arithmetic": "complex64 streams, f32 FFT butterflies, f64 Levinson-Durbin / tap solves",
-                       "caf_method": {1: "direct", 2: "fft"}.get(m, m),
-                       "doppler_method": {1: "rocfft"}.get(dp, dp),
-                       "parallelism": par},
-            "timed_seconds": dt,
-            # a rehearsal of the multi-rank control flow (gloo, ranks sharing a GPU): NOT a scaling number
-            "rehearsal": (f"{args.dist_backend} backend, {world} ranks on {torch.cuda.device_count()} GPU(s): control flow only, "
-                          f"not a number of record") if rehearsal else None,
-            # which code moved the maps (prc = prc_gather_frames: RCCL send/recv group through the C ABI; torch =
-            # torch.distributed.gather; none = single GPU or surfaces stay put) and every rank's own clock
-            "gather_path": gather_mode, "rccl_version": _lib.rccl_version() if gather_mode == "prc" else None,
-            # what RCCL itself reports for the communicator behind prc_gather_frames (ncclCommCount / ncclCommUserRank on
-            # every rank, all-gathered) and the bytes of maps every rank handed to the gather per step
-            "rccl_nranks": rccl_nranks, "rccl_ranks_seen": rccl_seen, "gathered_bytes_per_rank_per_step": gathered_bytes,
-            "rank_ms_per_step": [t / steps * 1e3 for t in rank_seconds],
+        result.update({
             # the whole step against the memory system, on the bytes MOVED per frame (counters: this run's passes or the
             # committed per-unit figures); SURVEY 8d's algorithmic accounting (two passes per Doppler bin; more bytes than the
             # fused chain moves, so its "fraction" can exceed what the chip can copy) is kept under its own name
@@ -1514,7 +1564,7 @@ def main():
                              "in_step_ms_per_launch": in_step[k_]["avg_ms"] if (in_step and k_ in in_step) else None}
                         for k_, v in kt.items()},
             "roofline": roof,
-        }
+        })
         solo_sum = sum(v["ms"] * v["launches_per_step"] for v in kt.values())
         result["kernel_time_accounting"] = {
             "solo_sum_ms_per_step": solo_sum, "ms_per_step": dt / steps * 1e3,

@@ -323,7 +323,7 @@ def test_bench_workload_modes_run(args, frames):
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--no-cpu", "--steps", "2", "--warmup", "1"] + args,
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--no-cpu", "--steps", "2", "--warmup", "1"] + args,
                        capture_output=True, text=True, timeout=600, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -332,6 +332,36 @@ def test_bench_workload_modes_run(args, frames):
     assert d["scaling"] == ("strong" if "cfg4" in args else "weak")
     assert d["roofline"]["bound"] in ("hbm", "valu") and 0 < d["roofline"]["frac"] < 1.5
     assert abs(d["value"] - frames * d["steps"] / d["timed_seconds"]) / d["value"] < 1e-6
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full, CPU leg not switched off) times exactly --steps steps and measures nothing else; its
+    --dump-outputs sample of the last step's maps (float32 values, float64 flat indices, under 64 MB) holds the same
+    cells as the maps --dump writes of that step"""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out, dump = tmp_path / "outputs", str(tmp_path / "cfg2.npz")
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "300",
+                        "--dump-outputs", str(out), "--dump", dump], capture_output=True, text=True, timeout=600, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] - d["timed_seconds"] / 3 * 1e3) < 1e-9 * d["ms_per_step"]
+    assert not [k for k in ("roofline", "kernels", "cpu_baseline", "secondary") if k in d], d.keys()
+    files = sorted(os.listdir(out))
+    assert files == ["maps.npy", "sample_index.npy"] and sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    vals, idx = np.load(out / "maps.npy"), np.load(out / "sample_index.npy").astype(np.int64)
+    assert vals.dtype == np.float32 and vals.shape == (1, idx.size, 2) and np.all(np.diff(idx) > 0)
+    g = np.load(dump)
+    cells = g["ill0_frames"][0].size
+    assert idx[-1] < 300 * cells
+    for j, f in enumerate(g["frame_index"]):
+        sel = idx // cells == f
+        assert sel.any()
+        got = vals[0, sel, 0] + 1j * vals[0, sel, 1]
+        assert np.array_equal(got, g["ill0_frames"][j].reshape(-1)[idx[sel] - f * cells]), int(f)
 
 
 def test_bench_cfg4_maps_against_an_independent_pass(tmp_path):
@@ -569,7 +599,7 @@ def test_bench_measures_its_own_traffic(tmp_path):
     """roofline.traffic used to be a constant from a file.  bench.py --traffic measure runs itself twice under
     `rocprofv3 --pmc` (FETCH_SIZE, then WRITE_SIZE: separate passes, counters only) on one launch's worth of frames and
     reports 2 x FETCH + WRITE of the dominant kernel -- the line says so, and the figure is the fused LS pass's 28-30 MB per
-    chunk-bin (the default line takes this path whenever its CPU leg runs: `--traffic auto`)."""
+    chunk-bin (a --full line takes this path whenever its CPU leg runs: `--traffic auto`)."""
     import json
     import shutil
     import subprocess
@@ -577,7 +607,7 @@ def test_bench_measures_its_own_traffic(tmp_path):
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 is not on PATH")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--no-cpu", "--steps", "2", "--warmup", "1", "--frames", "300",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--no-cpu", "--steps", "2", "--warmup", "1", "--frames", "300",
                         "--traffic", "measure"], capture_output=True, text=True, timeout=900, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -607,7 +637,7 @@ def test_bench_reports_in_step_kernel_durations():
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 is not on PATH")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--no-cpu", "--steps", "2", "--warmup", "1", "--frames", "1024",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--no-cpu", "--steps", "2", "--warmup", "1", "--frames", "1024",
                         "--traffic", "file", "--in-step", "measure"], capture_output=True, text=True, timeout=900, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

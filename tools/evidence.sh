@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 E=$R/gpurun_out/ev_$tag
 mkdir -p $E
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 run() {   # run <name> <command...>: stdout+stderr to <name>.log, the JSON line (if any) to <name>.json
   local name=$1; shift
   echo "$*" > $E/$name.cmd.txt
@@ -17,13 +17,13 @@ run() {   # run <name> <command...>: stdout+stderr to <name>.log, the JSON line 
 }
 trace() { # trace <name> <bench args...>
   local name=$1; shift
-  echo "rocprofv3 --kernel-trace --stats -- python bench.py $*" > $E/$name.cmd.txt
+  echo "rocprofv3 --kernel-trace --stats -- python bench.py --full $*" > $E/$name.cmd.txt
   rocprofv3 --kernel-trace --stats --output-format csv -d $E/$name -o t -- $B "$@" > $E/$name.log 2>&1
   grep '^{' $E/$name.log | tail -1 > $E/$name.json
 }
 pmc() {   # pmc <name> <bench args...>: one pass per counter group
   local name=$1; shift
-  echo "rocprofv3 --pmc <group> -- python bench.py $*   (one pass per group: FETCH_SIZE | WRITE_SIZE | SQ groups)" > $E/$name.cmd.txt
+  echo "rocprofv3 --pmc <group> -- python bench.py --full $*   (one pass per group: FETCH_SIZE | WRITE_SIZE | SQ groups)" > $E/$name.cmd.txt
   local i=0
   for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU" \
              "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
@@ -49,7 +49,7 @@ run bench_default $B --cpu-asis
 run bench_cfg3 $B --workload cfg3
 run bench_cfg4 $B --workload cfg4 --no-cpu
 run bench_cfg5 $B --workload cfg5
-run bench_prconfig $B --workload prconfig --steps 3
+run bench_prconfig $B --workload prconfig
 # one rank's share of the 600 s stream at 8 ranks: first, a middle and the (ragged) last shard
 for k in 0 3 7; do run bench_cfg4_shard${k}of8 $B --workload cfg4 --no-cpu --shard-of $k/8; done
 # shortFilt=False at config 2: the FFT segment kernel's long-FIR form against the time-domain kernel
@@ -67,7 +67,7 @@ trace trace_cfg3 --no-cpu --workload cfg3 --frames 512 --steps 1 --warmup 1
 trace trace_cfg5 --no-cpu --workload cfg5 --steps 20 --warmup 2
 trace trace_cfg5_lanes2 --no-cpu --workload cfg5 --steps 20 --warmup 2 --caf-lanes 2
 # the library's entry points as roctx ranges around the kernels they enqueue (PRC_OPT_MARKERS)
-echo "rocprofv3 --marker-trace --kernel-trace --stats -- python bench.py --markers --no-cpu --frames 512 --steps 2 --warmup 1" > $E/markers_cfg2.cmd.txt
+echo "rocprofv3 --marker-trace --kernel-trace --stats -- python bench.py --full --markers --no-cpu --frames 512 --steps 2 --warmup 1" > $E/markers_cfg2.cmd.txt
 rocprofv3 --marker-trace --kernel-trace --stats --output-format csv -d $E/markers_cfg2 -o t -- $B --markers --no-cpu --frames 512 --steps 2 --warmup 1 > $E/markers_cfg2.log 2>&1
 # 3. counters
 pmc pmc_cfg2 --no-cpu --frames 256 --steps 2 --warmup 1 --no-overlap
