@@ -34,8 +34,10 @@ struct CorrArgs {
     int32_t rot_p, rot_s1, rot_s2;     // apply the phase ramp (on the source index) or not
     int32_t circular;       // S index wraps modulo n, else zero beyond n
     PhaseRamp pr;
-    float2* partial;        // [batch][nblk][nS][nlags]
-    int32_t nblk;
+    float2* partial;        // [batch][nblk (x2 with split)][nS][nlags]
+    int32_t nblk;           // sample blocks (the grid); partial slots per batch item: nblk, or 2 nblk with split
+    int32_t split;          // write each block's double sum as two floats, hi in slot blk and lo = sum - hi in slot
+                            // nblk + blk: readers that add every slot in double then see the sum to ~48 bits
 };
 
 __device__ __forceinline__ float2 load_rot(const float2* __restrict__ src, int64_t m, int64_t n,
@@ -53,7 +55,9 @@ __global__ __launch_bounds__(LS_THREADS) void corr_partial_kernel(CorrArgs a) {
     float2* P = reinterpret_cast<float2*>(smem_raw);
     float2* S1 = P + LSC_TILE;
     float2* S2 = S1 + LSC_TILE + 64 * NLG;
-    float2* red = DUAL ? S2 + LSC_TILE + 64 * NLG : S2;   // 4 waves * (DUAL?2:1) * NLG * 64
+    // 4 waves * (DUAL?2:1) * NLG * 64 double sums, written once the tiles are done: they take the tile buffers' room
+    // (P, S1, S2 and a float-sized tail, which the launch sizes)
+    double2* red = reinterpret_cast<double2*>(smem_raw);
 
     constexpr int NS = DUAL ? 2 : 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -131,20 +135,28 @@ __global__ __launch_bounds__(LS_THREADS) void corr_partial_kernel(CorrArgs a) {
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int g = 0; g < NLG; ++g)
-                red[((wave * NS + s) * NLG + g) * 64 + lane] = make_float2((float)dacc[s][g].x, (float)dacc[s][g].y);
+                red[((wave * NS + s) * NLG + g) * 64 + lane] = dacc[s][g];
         __syncthreads();
+        // the four waves in double; the float partial loses the low bits of a ~1e5-sized sum, which on a badly
+        // conditioned reference (FM, OFDM guard bands) is an excess residual of 1e-5 .. 1e-4 -- hence `split`
+        const int slots = a.split ? 2 * a.nblk : a.nblk;
         for (int t = tid; t < NS * NLG * 64; t += LS_THREADS) {
-            float2 v = red[t];
+            double2 v = red[t];
 #pragma unroll
             for (int w = 1; w < 4; ++w) {
-                const float2 u = red[w * NS * NLG * 64 + t];
+                const double2 u = red[w * NS * NLG * 64 + t];
                 v.x += u.x;
                 v.y += u.y;
             }
             const int s = t / (NLG * 64);
             const int lag = L0 + (t - s * NLG * 64);
-            if (lag < a.nlags)
-                a.partial[(((int64_t)b * a.nblk + blk) * NS + s) * a.nlags + lag] = v;
+            if (lag < a.nlags) {
+                const float2 hi = make_float2((float)v.x, (float)v.y);
+                a.partial[(((int64_t)b * slots + blk) * NS + s) * a.nlags + lag] = hi;
+                if (a.split)
+                    a.partial[(((int64_t)b * slots + a.nblk + blk) * NS + s) * a.nlags + lag] =
+                        make_float2((float)(v.x - (double)hi.x), (float)(v.y - (double)hi.y));
+            }
         }
         __syncthreads();
     }
@@ -414,6 +426,67 @@ __global__ __launch_bounds__(LS_THREADS) void ls_prepare_kernel(LsPrepArgs a) {
     }
 }
 
+// ---- convergence guard of the refinement --------------------------------------------------------------------------
+// The host picks the number of refinement steps from |gamma - 1| 10 peek / N, which presumes a well-conditioned T_0.
+// On a coloured reference the iteration x += D T_0^{-1} D^H (b - T_f x) contracts far more slowly, or diverges: its
+// spectral radius is ~3e-3 on white noise but 0.5 on FM and 1.3 .. 4.6 on an OFDM-like reference with empty guard
+// carriers (40000 samples, bins of 1-2 Hz at 262 kHz; tests/test_chain_model.py).  So the solve kernels measure their
+// last two corrections: with q = |dx_k| / |dx_{k-1}| about q |dx_k| of error is left, and when that exceeds
+// CHAIN_TOL |x| the block's taps are recomputed by a Levinson solve of the exact Toeplitz(c_f) on one wavefront.
+// White references never take it (q |dx_k| ~ 1e-10 |x| or less); it costs two workgroup sums per step otherwise.
+// When it fires (on FM most blocks and bins do, even at 262144 samples) the bin costs a serial O(T^2) recursion on
+// one wavefront while the other fifteen wait -- correct, not fast; that cost is not measured by bench.py's white scenes.
+#define CHAIN_TOL2 1e-16                                   // CHAIN_TOL = 1e-8, squared
+
+// sum of v over the workgroup, returned to every thread (all threads must call it); red: LDS, >= 16 doubles
+__device__ double block_sum_d(double v, double* red) {
+    v = wave_allsum_d(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+    __syncthreads();
+    return s;
+}
+
+// Toeplitz(c) w = b, T[i][j] = c[i-j] (i >= j), conj(c[j-i]) (i < j), on wavefront 0 (the other waves return at once:
+// the caller synchronises).  The recursion of the oracle's levinson_hermitian; a0, a1: 2 T of LDS scratch for the
+// predictor, double-buffered.  c, b, w, a0, a1 in LDS.
+__device__ void levinson_solve_wave0(const double2* c, const double2* b, double2* w, double2* a0, double2* a1, int T) {
+    if ((threadIdx.x >> 6) != 0) return;
+    const int lane = threadIdx.x & 63;
+    for (int k = lane; k < T; k += 64) {
+        a0[k] = make_double2(k == 0 ? 1.0 : 0.0, 0.0);
+        a1[k] = a0[k];
+        w[k] = k == 0 ? zscale(b[0], 1.0 / c[0].x) : make_double2(0.0, 0.0);
+    }
+    __builtin_amdgcn_wave_barrier();
+    double err = c[0].x;
+    double2* ao = a0;
+    double2* an = a1;
+    for (int m = 1; m < T; ++m) {
+        double2 acc = make_double2(0, 0), res = make_double2(0, 0);
+        for (int i = lane; i < m; i += 64) {
+            acc = zadd(acc, zmul(ao[i], c[m - i]));
+            res = zadd(res, zmul(c[m - i], w[i]));
+        }
+        acc.x = wave_allsum_d(acc.x);
+        acc.y = wave_allsum_d(acc.y);
+        res.x = wave_allsum_d(res.x);
+        res.y = wave_allsum_d(res.y);
+        const double2 k = zscale(acc, -1.0 / err);
+        err = err * (1.0 - (k.x * k.x + k.y * k.y));
+        for (int j = lane; j <= m; j += 64) an[j] = zadd(ao[j], zmul(k, zconj(ao[m - j])));
+        __builtin_amdgcn_wave_barrier();
+        const double2 g = zscale(zsub(b[m], res), 1.0 / err);
+        for (int j = lane; j <= m; j += 64) w[j] = zadd(w[j], zmul(g, zconj(an[m - j])));
+        __builtin_amdgcn_wave_barrier();
+        double2* t = ao;
+        ao = an;
+        an = t;
+    }
+}
+
 struct LsSolveArgs {
     const float2* partial;   // slot 1 = conj( sum_n s~[n] conj(rho[n-k]) ), s~ = s e^{-j theta (n+peek)}
     const double2* c0;
@@ -443,6 +516,7 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_kernel(LsSolveArgs a) {
     // rows are spread over RP = T rounded up to a wavefront; the column range is cut into `parts`
     const int RP = (T + 63) & ~63;
     const int parts = LSS_THREADS / RP > 0 ? LSS_THREADS / RP : 1;
+    double* red = reinterpret_cast<double*>(pacc + (size_t)parts * RP);   // 16 doubles: workgroup sums
     const int row = tid % RP, part = tid / RP;
     const int span = (T + parts - 1) / parts;
     const int j0 = part * span, j1 = (j0 + span < T) ? j0 + span : T;
@@ -490,6 +564,8 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_kernel(LsSolveArgs a) {
         cf[k] = zmul(D, base);
     }
     __syncthreads();
+    bool fallback = false;
+    double dprev = 0.0;
     for (int it = 0; it <= a.nref; ++it) {
         // x (+)= D T_0^{-1} v   (T_0^{-1} is Hermitian: column `row` is read as conj(row-major [j][row]),
         // consecutive threads on consecutive addresses; 8 independent loads in flight per thread)
@@ -511,13 +587,25 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_kernel(LsSolveArgs a) {
             pacc[part * RP + row] = zadd(acc, acc2);
         }
         __syncthreads();
+        double dloc = 0.0, xloc = 0.0;
         if (tid < T) {
             double2 acc = pacc[tid];
             for (int q = 1; q < parts; ++q) acc = zadd(acc, pacc[q * RP + tid]);
             acc = zmul(dd[tid], acc);
-            x[tid] = it == 0 ? acc : zadd(x[tid], acc);
+            const double2 xn = it == 0 ? acc : zadd(x[tid], acc);
+            x[tid] = xn;
+            dloc = acc.x * acc.x + acc.y * acc.y;
+            xloc = xn.x * xn.x + xn.y * xn.y;
         }
         __syncthreads();
+        if (a.nref >= 1 && it >= a.nref - 1) {             // the convergence guard (see CHAIN_TOL2)
+            const double dn = block_sum_d(dloc, red);
+            if (it == a.nref) {
+                const double xn = block_sum_d(xloc, red);
+                fallback = !(dn * dn <= CHAIN_TOL2 * xn * dprev);
+            }
+            dprev = dn;
+        }
         if (it == a.nref) break;
         // residual against the exact Toeplitz(c_f):  v = D^H ( b - T_f x )
         if (active) {
@@ -542,6 +630,10 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_kernel(LsSolveArgs a) {
             for (int q = 0; q < parts; ++q) acc = zsub(acc, pacc[q * RP + tid]);
             v[tid] = zmul(zconj(dd[tid]), acc);
         }
+        __syncthreads();
+    }
+    if (fallback) {
+        levinson_solve_wave0(cf, bb, x, v, pacc, T);
         __syncthreads();
     }
     for (int k = tid; k < T; k += LSS_THREADS) {
@@ -675,6 +767,7 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_gs_kernel(LsGsArgs a) {
     }
     double2* stg_r = pacc + (size_t)parts * 4 * G;         // conj(ref[i]),            i < peek
     double2* stg_s = stg_r + a.peek;                       // s~[n - peek + i],        i < peek
+    double* red = reinterpret_cast<double*>(stg_s + a.peek);   // 16 doubles: workgroup sums
     if (a.theta != 0.0 && tid < 2 * a.peek) {
         if (tid < a.peek) {
             const float2 r = (a.ref + (int64_t)b * a.ref_stride)[tid];
@@ -739,6 +832,8 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_gs_kernel(LsGsArgs a) {
             for (int q = 0; q < parts; ++q) sum = zadd(sum, pacc[(size_t)q * 4 * G + tid]);
         return sum;                                        // caller stores, then __syncthreads()
     };
+    bool fallback = false;
+    double dprev = 0.0;
     for (int it = 0; it <= a.nref; ++it) {
         // x (+)= D T_0^{-1} v,   T_0^{-1} v = ( L(a) [L(a)^H v] - L(z) [L(z)^H v] ) / err
         {
@@ -753,12 +848,24 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_gs_kernel(LsGsArgs a) {
             const TriTerm ty0 = {A, PVp, 0};                                // sum_d a[d] p[i-d]
             const TriTerm ty1 = {Az, PVq, 1};                               // - sum_{d>=1} conj(a[T-d]) q[i-d]
             const double2 yk = product(ty0, false, &ty1, false);
+            double dloc = 0.0, xloc = 0.0;
             if (tid < T) {
                 const double2 acc = zmul(dd[tid], zscale(yk, ierr));
                 const int sl = gs_slot(tid, Q);
-                PVx[sl] = it == 0 ? acc : zadd(PVx[sl], acc);
+                const double2 xn = it == 0 ? acc : zadd(PVx[sl], acc);
+                PVx[sl] = xn;
+                dloc = acc.x * acc.x + acc.y * acc.y;
+                xloc = xn.x * xn.x + xn.y * xn.y;
             }
             __syncthreads();
+            if (a.nref >= 1 && it >= a.nref - 1) {         // the convergence guard (see CHAIN_TOL2)
+                const double dn = block_sum_d(dloc, red);
+                if (it == a.nref) {
+                    const double xn = block_sum_d(xloc, red);
+                    fallback = !(dn * dn <= CHAIN_TOL2 * xn * dprev);
+                }
+                dprev = dn;
+            }
         }
         if (it == a.nref) break;
         // residual against the exact Toeplitz(c_f):  v = D^H ( b - T_f x ),  (T_f x)[i] = sum_{d<=i} c_f[d] x[i-d] +
@@ -771,8 +878,12 @@ __global__ __launch_bounds__(LSS_THREADS) void ls_solve_gs_kernel(LsGsArgs a) {
             __syncthreads();
         }
     }
+    if (fallback) {                                        // A, Ac, Ar are free now: predictor scratch and solution
+        levinson_solve_wave0(CF, bb, Ar, A, Ac, T);
+        __syncthreads();
+    }
     for (int k = tid; k < T; k += LSS_THREADS) {
-        const double2 xk = PVx[gs_slot(k, Q)];
+        const double2 xk = fallback ? Ar[k] : PVx[gs_slot(k, Q)];
         a.taps[(int64_t)b * T + k] = xk;
         a.taps_t[(int64_t)b * T + k] = zmul(xk, zconj(dd[k]));
     }
@@ -990,7 +1101,8 @@ static int ls_plan_create_impl(prc_ls_plan** plan, const prc_ls_desc* d, bool al
     }
     p->fft_waves = p->team_chain ? ls_team_chain_teams_per_block(d->n, p->team_piece, d->max_blocks, (int)prc_opt(PRC_OPT_LS_TEAM_PIECES))
                    : p->team     ? ls_team_teams_per_block(d->n, T) : ls_fft_waves_per_block(d->n, T);
-    p->nblk = p->method == 2 ? p->fft_waves : (int)ceil_div64(d->n, LSC_BLK);
+    // time-domain kernels: two float slots per sample block (CorrArgs::split), added in double by the solvers
+    p->nblk = p->method == 2 ? p->fft_waves : 2 * (int)ceil_div64(d->n, LSC_BLK);
     hipError_t e = hipMalloc(&p->d_partial, sizeof(float2) * (size_t)d->max_blocks * p->nblk * 2 * T);
     if (e == hipSuccess) e = hipMalloc(&p->d_taps, sizeof(double2) * (size_t)d->max_blocks * T);
     if (e == hipSuccess) e = hipMalloc(&p->d_rhs, sizeof(double2) * (size_t)d->max_blocks * T);
@@ -1009,7 +1121,7 @@ static int ls_plan_create_impl(prc_ls_plan** plan, const prc_ls_desc* d, bool al
         p->gs_span = (T + p->gs_parts - 1) / p->gs_parts;
         p->gs_Q = (T + 8 + 3) / 4;
         p->gs_lds = sizeof(double2) * ((size_t)8 * T + 16 * (size_t)p->gs_Q +
-                                       (size_t)p->gs_parts * 4 * p->gs_G + 2 * (size_t)d->peek);
+                                       (size_t)p->gs_parts * 4 * p->gs_G + 2 * (size_t)d->peek + 8);
         const bool use_gs = p->gs_lds <= 160 * 1024 && p->gs_G <= LSS_THREADS;
         if (use_gs) {
             if (e == hipSuccess) e = hipMalloc(&p->d_apred, sizeof(double2) * (size_t)d->max_blocks * T);
@@ -1103,7 +1215,7 @@ static int run_cached_chain(prc_ls_plan* p, const void* ref, const void* srv, in
     const int64_t n = p->desc.n;
     const int RP = (T + 63) & ~63;
     const int parts = LSS_THREADS / RP > 0 ? LSS_THREADS / RP : 1;
-    const size_t solve_lds = sizeof(double2) * ((size_t)5 * T + (size_t)parts * RP);
+    const size_t solve_lds = sizeof(double2) * ((size_t)5 * T + (size_t)parts * RP + 8);
     auto theta_exact = [&](int i) { return 2.0 * 3.14159265358979323846 * bins[i] / sample_rate; };
     auto launch_solve = [&](int i, const float2* cur, int64_t cur_stride) -> int {
         const PhaseRamp pr = make_ramp(bins[i], sample_rate, 0.0);
@@ -1264,7 +1376,8 @@ extern "C" int prc_ls_execute(prc_ls_plan* p, const void* ref, const void* srv, 
                 ca.circular = p->desc.circular;
                 ca.pr = pr;
                 ca.partial = p->d_partial;
-                ca.nblk = p->nblk;
+                ca.nblk = p->nblk / 2;
+                ca.split = 1;
                 rc = launch_corr(ca, true, nblocks, stream);
             }
             if (rc) return rc;

@@ -104,16 +104,57 @@ def make_fm_scene(n, sample_rate, rangeBins, seed, deviation=75e3, audio_bw=15e3
     audio /= 3.0 * np.std(audio)                      # +-1 at three sigma
     phase = 2 * np.pi * deviation * np.cumsum(audio) / sample_rate
     ref = np.exp(1j * phase).astype(np.complex64)
-    noise = _cwhite(gen, n)
-    targets = kw.get("targets", default_targets(rangeBins))
+    return ref, _echo_channel(ref, _cwhite(gen, n), sample_rate, rangeBins, **kw)
+
+
+def make_ofdm_scene(n, sample_rate, rangeBins, seed, nfft=256, guard=0.25, ref_noise_db=-60.0, **kw):
+    """Scene on an OFDM-like illuminator (DAB / DVB-T style): ``nfft``-point symbols with a cyclic prefix of nfft/8,
+    unit-power QPSK on the occupied carriers and the outer ``guard`` fraction of the band left empty, passed through
+    an ideal (circular, brick-wall) transmit mask of the same occupied band so that symbol edges leak nothing into
+    the guard band; plus white reference-channel noise ``ref_noise_db`` below the signal.  The empty band makes the
+    autocorrelation matrix nearly singular; the noise floor bounds its condition number (~ 10^(-ref_noise_db/10)),
+    so that a float64 Toeplitz solve is still meaningful.  Unit power, complex64; echoes as in make_fm_scene."""
+    gen = np.random.Generator(np.random.Philox(key=seed))
+    cp = nfft // 8
+    nsym = -(-n // (nfft + cp))
+    half = 0.5 * (1.0 - guard)                       # occupied band: |f| <= half (cycles per sample)
+    used = np.abs(np.fft.fftfreq(nfft)) <= half
+    qpsk = np.sign(gen.standard_normal((nsym, nfft))) + 1j * np.sign(gen.standard_normal((nsym, nfft)))
+    sym = np.fft.ifft(qpsk * used, axis=1)
+    x = np.concatenate([sym[:, nfft - cp:], sym], axis=1).reshape(-1)[:n]
+    x = np.fft.ifft(np.fft.fft(x) * (np.abs(np.fft.fftfreq(n)) <= half))
+    x /= np.sqrt(np.mean(np.abs(x) ** 2))
+    ref = (x + 10.0 ** (ref_noise_db / 20.0) * _cwhite(gen, n)).astype(np.complex64)
+    return ref, _echo_channel(ref, _cwhite(gen, n), sample_rate, rangeBins, **kw)
+
+
+def make_ar2_scene(n, sample_rate, rangeBins, seed, radius=0.99, pole_freq=0.1, **kw):
+    """Scene on an AR(2) illuminator: complex white noise through 1 / (1 - 2 r cos(w) z^-1 + r^2 z^-2), poles at
+    r e^{+-j w} (w = 2 pi ``pole_freq`` cycles per sample), applied circularly in the frequency domain (stationary
+    from the first sample).  Two narrow resonances ~40 dB above the spectrum's floor at r = 0.99.  Unit power,
+    complex64; echoes as in make_fm_scene."""
+    gen = np.random.Generator(np.random.Philox(key=seed))
+    w = np.fft.fft(_cwhite(gen, n).astype(np.complex128))
+    z = np.exp(-2j * np.pi * np.fft.fftfreq(n))
+    a = 1.0 - 2.0 * radius * np.cos(2 * np.pi * pole_freq) * z + radius * radius * z * z
+    x = np.fft.ifft(w / a)
+    ref = (x / np.sqrt(np.mean(np.abs(x) ** 2))).astype(np.complex64)
+    return ref, _echo_channel(ref, _cwhite(gen, n), sample_rate, rangeBins, **kw)
+
+
+def _echo_channel(ref, noise, sample_rate, rangeBins, targets=None, clutter=DEFAULT_CLUTTER, noise_amp=0.003):
+    """srv = clutter echoes + moving targets (circular delays, as make_scene) + noise_amp * noise, complex64"""
+    n = ref.shape[0]
+    if targets is None:
+        targets = default_targets(rangeBins)
     acc = np.zeros(n, dtype=np.complex128)
-    for d, a in kw.get("clutter", DEFAULT_CLUTTER):
+    for d, a in clutter:
         acc += a * np.roll(ref, d)
     t = np.arange(n, dtype=np.float64) / float(sample_rate)
     for d, fd, a in targets:
         acc += a * np.roll(ref, d) * np.exp(2j * np.pi * fd * t)
-    acc += kw.get("noise_amp", 0.003) * noise
-    return ref, acc.astype(np.complex64)
+    acc += noise_amp * noise
+    return acc.astype(np.complex64)
 
 
 def make_raw_stream(nchunks, input_chunk_length, input_sample_rate, offset_freq, seed, channel_bw=200e3,
