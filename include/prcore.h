@@ -43,7 +43,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 600   /* 600: every descriptor (prc_caf_desc, prc_ls_desc, prc_frontend_desc, prc_iir_desc) starts with `struct_size`,
+#define PRC_VERSION 610   /* 610: prc_track_desc, prc_track_record, prc_track_plan_create / _destroy, prc_track_measure, prc_track_run
+                             (get_measurements and multitarget_tracker on device);
+                             600: every descriptor (prc_caf_desc, prc_ls_desc, prc_frontend_desc, prc_iir_desc) starts with `struct_size`,
                              `magic` (layout break: rebuild hosts; from here on descriptors only grow at the end and an older host keeps
                              working); PRC_OPT_CAF_TEAM8; host arrays passed to an entry point are read before it returns;
                              500: prc_frequency_shift_phases, prc_frontend_execute2, prc_cfar2d_c64, prc_mem_info, PRC_OPT_MARKERS; 401: prc_comm_loopback, PRC_OPT_FE_METHOD, PRC_OPT_CFAR_METHOD; 400: prc_caf_desc.multi, prc_set_option / prc_get_option (no environment variables are read),
@@ -390,6 +392,65 @@ int prc_comm_destroy(prc_comm* comm);
  * copy (skipped when send already points at its slot in recv). */
 int prc_gather_frames(prc_comm* comm, const void* send, const int64_t* frames_per_rank_host,
                       int64_t frame_elems, void* recv, int32_t root, void* stream);
+
+/* ---- target tracking: target_detection.py:164-537 (get_measurements, multitarget_tracker) ---------------------- */
+/* Frames are float32 [nframes][H][W] (H = Doppler rows, W = range columns), the layout prc_cfar2d / prc_cfar2d_c64
+ * write.  prc_track_measure reproduces get_measurements (:190-227) per frame: mean |v| over the whole frame (fp64), the
+ * reference's fliplr(frame.T) orientation with range rows [:8] and [-8:] and Doppler columns [H/2-4, H/2+4) zeroed,
+ * numpy's linear percentile from the exact order statistics x(k), x(k+1) (radix select), and every cell with
+ * v/mean >= threshold, sorted by descending strength, ties by descending flat index (r*H + c in fliplr(T) row-major
+ * order: np.flip(np.argsort(s, kind="stable"))).  A frame holding a NaN or Inf, or of mean 0, has no candidates.
+ * prc_track_run is multitarget_tracker (:455-537) on those lists: one wavefront walks all frames in order, the track
+ * state stays on the device, everything in fp64. */
+typedef struct prc_track_desc {
+    uint32_t struct_size;  /* sizeof(prc_track_desc) as the host compiled it (see Conventions)          */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                       */
+    int32_t H, W;          /* frame shape: Doppler rows (>= 8), range columns (>= 17)              */
+    int32_t ntracks;       /* 1 .. 64                                                              */
+    int32_t capacity;      /* candidates stored per frame (>= 1)                                   */
+    double percentile;     /* in [0, 100]; the tracker's own call uses 99.8                        */
+    double doppler_extent; /* frame_extent[0] (Hz): Doppler coordinates np.linspace(-D, D, H)       */
+    double range_extent;   /* frame_extent[1] (km): range coordinates np.linspace(R, 0, W)          */
+} prc_track_desc;
+#define PRC_TRACK_DESC_SIZE_610 48u
+
+/* one candidate: strength v/mean, its coordinates (numpy 2.x linspace bitwise), flat index r*H + c of fliplr(T) */
+typedef struct prc_track_cand {
+    double strength, range, doppler;
+    int64_t index;
+} prc_track_cand;
+#define PRC_TRACK_CAND_SIZE 32u
+
+/* the state of one track after one frame (target_track_dtype + kalman_filter_dtype; F1, F2, Q, H, R are constants) */
+typedef struct prc_track_record {
+    int32_t status;          /* 0 free, 1 preliminary, 2 confirmed                                     */
+    int32_t lifetime;
+    double measurement[2];   /* range (km), Doppler (Hz)                                               */
+    double estimate[2];
+    double x[4];
+    double P[16];            /* row-major 4 x 4                                                        */
+    double S[4];             /* row-major 2 x 2                                                        */
+    uint8_t history[20];     /* measurement_history: 1 where a measurement was assigned, newest first  */
+    int32_t overflow;        /* 1: this frame had more candidates than the plan's capacity; the first
+                                `capacity` (in strength order) were used                               */
+} prc_track_record;
+#define PRC_TRACK_RECORD_SIZE 256u
+
+typedef struct prc_track_plan prc_track_plan;
+/* PRC_EINVAL for H < 8 or W < 17 (the reference's mask slices go negative or overlap), ntracks outside 1..64, a
+ * percentile outside [0, 100] or capacity < 1.  Any capacity works: above 2^19 the plan allocates a device workspace of
+ * capacity / 8 bytes for prc_track_run's per-candidate bits (below, they sit in LDS). */
+int prc_track_plan_create(prc_track_plan** plan, const prc_track_desc* desc);
+int prc_track_plan_destroy(prc_track_plan* plan);
+/* frames: DEVICE float32 [nframes][H][W]; counts: DEVICE int32 [nframes] = the TRUE candidate count of each frame (may
+ * exceed capacity); cands: DEVICE prc_track_cand [nframes][capacity], the first min(count, capacity) written.  Neither
+ * allocates nor synchronises. */
+int prc_track_measure(prc_track_plan* plan, const float* frames, int32_t nframes, int32_t* counts,
+                      prc_track_cand* cands, void* stream);
+/* counts / cands as prc_track_measure wrote them; records: DEVICE prc_track_record [nframes][ntracks].  The tracks
+ * start free (initialize_track(None)) at every call. */
+int prc_track_run(prc_track_plan* plan, const int32_t* counts, const prc_track_cand* cands, int32_t nframes,
+                  prc_track_record* records, void* stream);
 
 #ifdef __cplusplus
 }

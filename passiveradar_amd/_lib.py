@@ -74,7 +74,30 @@ class IirDesc(_Desc):
                 ("poles_host", C.POINTER(C.c_double)), ("gain", C.c_double)]
 
 
-MIN_LIB_VERSION = 600      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+class TrackDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("H", C.c_int32), ("W", C.c_int32), ("ntracks", C.c_int32), ("capacity", C.c_int32),
+                ("percentile", C.c_double), ("doppler_extent", C.c_double), ("range_extent", C.c_double)]
+
+
+class TrackCand(C.Structure):
+    _fields_ = [("strength", C.c_double), ("range", C.c_double), ("doppler", C.c_double), ("index", C.c_int64)]
+
+
+class TrackRecord(C.Structure):
+    _fields_ = [("status", C.c_int32), ("lifetime", C.c_int32), ("measurement", C.c_double * 2),
+                ("estimate", C.c_double * 2), ("x", C.c_double * 4), ("P", C.c_double * 16), ("S", C.c_double * 4),
+                ("history", C.c_uint8 * 20), ("overflow", C.c_int32)]
+
+
+# NumPy views of prc_track_cand / prc_track_record (same layout as the ctypes mirrors)
+TRACK_CAND_DTYPE = np.dtype([("strength", "<f8"), ("range", "<f8"), ("doppler", "<f8"), ("index", "<i8")])
+TRACK_RECORD_DTYPE = np.dtype([("status", "<i4"), ("lifetime", "<i4"), ("measurement", "<f8", (2,)),
+                               ("estimate", "<f8", (2,)), ("x", "<f8", (4,)), ("P", "<f8", (16,)), ("S", "<f8", (4,)),
+                               ("history", "u1", (20,)), ("overflow", "<i4")])
+
+
+MIN_LIB_VERSION = 610      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -141,6 +164,10 @@ _SIGNATURES = {
                             C.c_void_p]),
     "prc_frequency_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                       C.c_double, C.c_void_p]),
+    "prc_track_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(TrackDesc)]),
+    "prc_track_plan_destroy": (C.c_int, [C.c_void_p]),
+    "prc_track_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "prc_track_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),

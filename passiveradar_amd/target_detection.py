@@ -1,14 +1,18 @@
-"""Drop-in for the one function of the reference's ``passiveRadar/target_detection.py`` that sits next
-to the range-Doppler path (SURVEY 8f "next" #3): ``CFAR_2D`` (:683-703), applied per frame to
-``|xambg|`` by range_doppler_plot.py:56-57.  The Kalman trackers of that module are out of scope."""
+"""Drop-ins for the reference's ``passiveRadar/target_detection.py``: ``CFAR_2D`` (:683-703), applied per frame to
+``|xambg|`` by range_doppler_plot.py:56-57 (SURVEY 8f "next" #3), and the multi-target Kalman tracker of
+multitarget_kalman_tracker.py: ``get_measurements`` (:164-229) and ``multitarget_tracker`` (:455-537), plus
+``track_maps``, that script's CFAR -> measure -> track chain (:44-63) in one device pass."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
 from . import _lib, engine
 from ._lib import check, lib
 
-__all__ = ["CFAR_2D", "CFAR_2D_abs"]
+__all__ = ["CFAR_2D", "CFAR_2D_abs", "get_measurements", "multitarget_tracker", "track_maps",
+           "kalman_filter_dtype", "target_track_dtype"]
 
 
 def CFAR_2D(X, fw, gw, thresh=None):
@@ -68,3 +72,232 @@ def CFAR_2D_abs(xambg, fw, gw, thresh=None):
                                do.ptr, frames, None))
     out = do.download(x.shape, np.float32)
     return out > 0.5 if thresh is not None else out.astype(np.float64)
+
+
+# ---- multi-target tracker (target_detection.py:164-537) ---------------------------------------------------------------
+# the reference's record types (np.float -> float64, np.int -> int64)
+kalman_filter_dtype = np.dtype([("x", np.float64, (4,)), ("P", np.float64, (4, 4)), ("F1", np.float64, (4, 4)),
+                                ("F2", np.float64, (4, 4)), ("Q", np.float64, (4, 4)), ("H", np.float64, (2, 4)),
+                                ("R", np.float64, (2, 2)), ("S", np.float64, (2, 2))])
+target_track_dtype = np.dtype([("status", np.int64), ("lifetime", np.int64), ("measurement", np.float64, (2,)),
+                               ("estimate", np.float64, (2,)), ("measurement_history", np.float64, (20,)),
+                               ("kalman_state", kalman_filter_dtype)])
+# the constants of initialize_track (:375-382)
+_F1 = np.array([[1, 0, -0.003, 0], [0, 0, -0.003, -0.003], [0, 0, 1, 1], [0, 0, 0, 1]], dtype=np.float64)
+_F2 = np.array([[1, 1, 0, 0], [0, 1, 0, 0], [0, 0, 1, 1], [0, 0, 0, 1]], dtype=np.float64)
+_Q = np.diag([4.0, 0.03, 0.2, 0.08])
+_H = np.array([[1, 0, 0, 0], [0, 0, 1, 0]], dtype=np.float64)
+_R = np.diag([5.0, 2.0])
+TRACK_PERCENTILE = 99.8        # get_measurements ignores its `p` and always takes the 99.8th percentile (:211)
+
+
+class TrackPlan:
+    """Owner of a prc_track_plan (frame shape, track count, candidate capacity, extents).  Any capacity >= 1 works:
+    above 2^19 candidates per frame (a threshold on a long run of ties in a frame of more than 2^19 cells) the plan
+    allocates a device workspace of capacity / 8 bytes for the tracker's per-candidate bits, which otherwise sit in LDS."""
+
+    def __init__(self, H, W, ntracks, capacity, frame_extent, percentile=TRACK_PERCENTILE):
+        d = _lib.TrackDesc()
+        d.H, d.W, d.ntracks, d.capacity = int(H), int(W), int(ntracks), int(capacity)
+        d.percentile = float(percentile)
+        d.doppler_extent, d.range_extent = float(frame_extent[0]), float(frame_extent[1])
+        self.H, self.W, self.ntracks, self.capacity = d.H, d.W, d.ntracks, d.capacity
+        h = C.c_void_p()
+        check(lib().prc_track_plan_create(C.byref(h), C.byref(d)))
+        self.handle = h.value
+
+    def measure(self, frames, nframes, counts, cands, stream=None):
+        check(lib().prc_track_measure(self.handle, frames, int(nframes), counts, cands, stream))
+
+    def run(self, counts, cands, nframes, records, stream=None):
+        check(lib().prc_track_run(self.handle, counts, cands, int(nframes), records, stream))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().prc_track_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def expected_capacity(H, W, percentile=TRACK_PERCENTILE):
+    """candidates a tie-free frame has at the percentile (n - 1 - k), plus a margin"""
+    n = int(H) * int(W)
+    k = int(np.floor(np.float64(n - 1) * np.true_divide(np.float64(percentile), 100)))
+    return max(1, n - 1 - k) + 64
+
+
+def _frames_shape(x):
+    if x.ndim == 2:
+        return 1, x.shape[0], x.shape[1]
+    if x.ndim == 3:
+        return x.shape[0], x.shape[1], x.shape[2]
+    raise ValueError("expected a frame [H, W] or a stack [nframes, H, W]")
+
+
+class _Measured:
+    """counts + candidate records of a stack of frames on the device, measured with a plan whose capacity holds every
+    frame's candidates: after one measure the counts are read, and if any exceeds the capacity the plan is rebuilt at
+    the exact maximum and the stack measured again (a deterministic sizing step).  ``capacity`` pins the capacity (no
+    rebuild: frames over it keep their first `capacity` candidates and the tracker flags them); ``start_capacity`` only
+    replaces the first guess (default: expected_capacity)."""
+
+    def __init__(self, frames_ptr, nframes, H, W, frame_extent, ntracks, alloc, stream, percentile=TRACK_PERCENTILE,
+                 capacity=None, start_capacity=None):
+        self.alloc, self.stream = alloc, stream
+        self.nframes = nframes
+        self.rebuilt = False
+        cap = int(capacity or start_capacity or expected_capacity(H, W, percentile))
+        self.counts_buf = alloc("counts", 4 * max(nframes, 1))
+        for attempt in range(2):
+            self.plan = TrackPlan(H, W, ntracks, cap, frame_extent, percentile)
+            self.cands_buf = alloc("cands", 32 * max(nframes, 1) * cap)
+            self.plan.measure(frames_ptr, nframes, self.counts_buf.ptr, self.cands_buf.ptr, stream)
+            self.counts = self.counts_buf.download(nframes, np.int32, stream=stream)
+            need = int(self.counts.max()) if nframes else 0
+            if need <= cap or capacity:
+                break
+            cap = need
+            self.rebuilt = True
+        self.capacity = cap
+
+    def candidates(self):
+        raw = self.cands_buf.download(self.nframes * self.capacity, _lib.TRACK_CAND_DTYPE, stream=self.stream)
+        return raw.reshape(self.nframes, self.capacity)
+
+    def run(self):
+        rec = self.alloc("records", 256 * max(self.nframes, 1) * self.plan.ntracks)
+        self.plan.run(self.counts_buf.ptr, self.cands_buf.ptr, self.nframes, rec.ptr, self.stream)
+        out = rec.download(self.nframes * self.plan.ntracks, _lib.TRACK_RECORD_DTYPE, stream=self.stream)
+        return out.reshape(self.nframes, self.plan.ntracks)
+
+
+class _TorchBuf:
+    """a device byte buffer from torch's allocator with DeviceBuffer's download()"""
+
+    def __init__(self, nbytes, device):
+        import torch
+        self.t = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+        self.ptr = self.t.data_ptr()
+
+    def download(self, shape, dtype, stream=None):
+        out = np.empty(shape, dtype=dtype)
+        check(lib().prc_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes, stream))
+        check(lib().prc_stream_sync(stream))
+        return out
+
+
+def _device_measure(x, frame_extent, ntracks=1, capacity=None, percentile=TRACK_PERCENTILE, start_capacity=None):
+    """measure a 2-D frame or [nframes, H, W] stack: numpy (staged) or a torch device tensor (on its stream)"""
+    if _lib.is_device_tensor(x):
+        import torch
+        t = x.to(torch.float32).contiguous()
+        nframes, H, W = _frames_shape(t)
+        stream = _lib.torch_stream_ptr(t.device)
+        with torch.cuda.device(t.device):
+            m = _Measured(t.data_ptr(), nframes, H, W, frame_extent, ntracks, lambda name, nb: _TorchBuf(nb, t.device),
+                          stream, percentile, capacity, start_capacity)
+        m.keep = t
+        return m
+    f = np.ascontiguousarray(x, dtype=np.float32)
+    nframes, H, W = _frames_shape(f)
+    _lib.require_gpu()
+    dx = _lib.DeviceBuffer(f.nbytes)
+    dx.upload(f)
+    m = _Measured(dx.ptr, nframes, H, W, frame_extent, ntracks, lambda name, nb: _lib.DeviceBuffer(nb), None,
+                  percentile, capacity, start_capacity)
+    m.keep = dx
+    return m
+
+
+def _cands_to_meas(c, count):
+    c = c[:count]
+    return np.stack((c["range"], c["doppler"], c["strength"]))
+
+
+def get_measurements(dataFrame, p, frame_extent):
+    """get_measurements (target_detection.py:164-229): candidate measurements of one range-Doppler frame (H Doppler rows
+    x W range columns) as (3, M) float64 -- range, Doppler, strength, strongest first (ties: the later cell of the
+    reference's fliplr(frame.T) order first).  ``p`` is ignored, as in the reference (always the 99.8th percentile).
+    A torch device stack [N, H, W] returns ``(counts, meas, index)`` on the device instead: int32 [N], float64
+    [N, 3, capacity] (range, Doppler, strength; entries past counts[i] unused) and int64 [N, capacity] flat indices."""
+    if _lib.is_device_tensor(dataFrame):
+        import torch
+        m = _device_measure(dataFrame, frame_extent)
+        raw = m.cands_buf.t[:32 * m.nframes * m.capacity].view(torch.float64).view(m.nframes, m.capacity, 4)
+        meas = raw[:, :, [1, 2, 0]].permute(0, 2, 1).contiguous()
+        index = m.cands_buf.t[:32 * m.nframes * m.capacity].view(torch.int64).view(m.nframes, m.capacity, 4)[:, :, 3]
+        counts = m.counts_buf.t[:4 * m.nframes].view(torch.int32).clone()
+        return counts, meas, index.contiguous()
+    x = np.asarray(dataFrame)
+    if x.ndim != 2:
+        raise ValueError("get_measurements takes one 2-D frame (a torch device stack for batches)")
+    m = _device_measure(x, frame_extent)
+    return _cands_to_meas(m.candidates()[0], int(m.counts[0]))
+
+
+def _records_to_history(rec, ntracks):
+    out = np.zeros(rec.shape, dtype=target_track_dtype)
+    out["status"] = rec["status"]
+    out["lifetime"] = rec["lifetime"]
+    out["measurement"] = rec["measurement"]
+    out["estimate"] = rec["estimate"]
+    out["measurement_history"] = rec["history"].astype(np.float64)
+    ks = out["kalman_state"]
+    ks["x"] = rec["x"]
+    ks["P"] = rec["P"].reshape(rec.shape + (4, 4))
+    ks["S"] = rec["S"].reshape(rec.shape + (2, 2))
+    ks["F1"], ks["F2"], ks["Q"], ks["H"], ks["R"] = _F1, _F2, _Q, _H, _R
+    out["kalman_state"] = ks
+    if rec["overflow"].any():
+        raise _lib.PrcoreError(_lib.PRC_EINVAL, "multitarget_tracker: a frame's candidates exceeded the plan's capacity")
+    return out
+
+
+def multitarget_tracker(data, frame_extent, N_TRACKS):
+    """multitarget_tracker (target_detection.py:455-537): ``data`` is numpy (H, W, Nframes) as the reference takes it
+    (converted to float32), or a torch device tensor [N, H, W]; frame_extent = [max Doppler, max range].  Returns the
+    reference's (Nframes, N_TRACKS) array of target_track_dtype."""
+    if _lib.is_device_tensor(data):
+        x = data
+    else:
+        d = np.asarray(data)
+        if d.ndim != 3:
+            raise ValueError("multitarget_tracker takes (H, W, Nframes) frames")
+        x = np.moveaxis(d, 2, 0)
+    m = _device_measure(x, frame_extent, int(N_TRACKS))
+    return _records_to_history(m.run(), int(N_TRACKS))
+
+
+def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4):
+    """multitarget_kalman_tracker.py:44-63 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per
+    frame (CFAR_2D_abs; CFAR_2D for a real magnitude stack) -> get_measurements -> multitarget_tracker.  ``xambg`` is a
+    torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it."""
+    if _lib.is_device_tensor(xambg):
+        import torch
+        cf = CFAR_2D_abs(xambg, fw, gw) if xambg.is_complex() else CFAR_2D(xambg, fw, gw)
+        if cf.dim() == 2:
+            cf = cf.unsqueeze(0)
+        return multitarget_tracker(cf, frame_extent, N_TRACKS)
+    x = np.moveaxis(np.asarray(xambg), 2, 0)
+    _lib.require_gpu()
+    if np.iscomplexobj(x):
+        xc = np.ascontiguousarray(x, dtype=np.complex64)
+        nframes, H, W = xc.shape
+        dx = _lib.DeviceBuffer(xc.nbytes)
+        dx.upload(xc)
+        do = _lib.DeviceBuffer(nframes * H * W * 4)
+        check(lib().prc_cfar2d_c64(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    else:
+        xf = np.ascontiguousarray(x, dtype=np.float32)
+        nframes, H, W = xf.shape
+        dx = _lib.DeviceBuffer(xf.nbytes)
+        dx.upload(xf)
+        do = _lib.DeviceBuffer(xf.nbytes)
+        check(lib().prc_cfar2d(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    m = _Measured(do.ptr, nframes, H, W, frame_extent, int(N_TRACKS), lambda name, nb: _lib.DeviceBuffer(nb), None)
+    return _records_to_history(m.run(), int(N_TRACKS))
