@@ -43,7 +43,8 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 610   /* 610: prc_track_desc, prc_track_record, prc_track_plan_create / _destroy, prc_track_measure, prc_track_run
+#define PRC_VERSION 620   /* 620: prc_gal_execute, prc_gal_workspace_bytes (GAL_JPE on device);
+                             610: prc_track_desc, prc_track_record, prc_track_plan_create / _destroy, prc_track_measure, prc_track_run
                              (get_measurements and multitarget_tracker on device);
                              600: every descriptor (prc_caf_desc, prc_ls_desc, prc_frontend_desc, prc_iir_desc) starts with `struct_size`,
                              `magic` (layout break: rebuild hosts; from here on descriptors only grow at the end and an older host keeps
@@ -264,6 +265,23 @@ int prc_nlms_execute(const void* ref, const void* srv, int64_t n, int64_t stride
                      int32_t filter_len, int32_t peek, float mu, const void* taps_in,
                      void* out, int64_t out_stride, void* taps_out, int32_t nstreams,
                      void* stream);
+
+/* ---- GAL_JPE (clutter_removal.py:251-365) --------------------------------------------- */
+/* nstreams independent gradient-adaptive-lattice joint-process estimators: lattice_len reflection coefficients k, then a
+ * transversal NLMS stage of delay_len taps h over the lattice's backward errors (1 <= lattice_len <= delay_len).  Per
+ * sample n < n - peek - 1 the input is ref[n + peek] and the output out[n] = srv[n] - h^H b; every element of out in
+ * [0, n) is written (zero from n - peek - 1 on).  mu1 / mu2 are the lattice / transversal step sizes (mu1 evolves as the
+ * reference's complex mu1 = min(0.999 mu1 + 1e-8 e^2, 5e-3)).  Everything is complex64 (float2) on the device.
+ * k_out, h_out: optional complex64 [nstreams][delay_len], the final k (k[0] = 0) and h.
+ * delay_len <= 2048: one wavefront per stream, state in registers, no workspace.  Above: one workgroup per stream, state in
+ * `workspace`, prc_gal_workspace_bytes(delay_len, nstreams) bytes of device memory owned by the caller (NULL when that
+ * count is 0; it must not be shared by calls in flight).  Neither allocates nor synchronises.
+ * PRC_EINVAL: null pointers, non-positive sizes, negative peek, a missing workspace; PRC_ESHAPE: lattice_len > delay_len
+ * or a stride shorter than n. */
+int prc_gal_workspace_bytes(int32_t delay_len, int32_t nstreams, size_t* bytes);
+int prc_gal_execute(const void* ref, const void* srv, int64_t n, int64_t stride, int32_t lattice_len,
+                    int32_t delay_len, int32_t peek, float mu1, float mu2, void* out, int64_t out_stride,
+                    void* k_out, void* h_out, int32_t nstreams, void* workspace, void* stream);
 
 /* ---- helpers that sit on the path (signal_utils.py) ---------------------------------- */
 /* xcorr (:29-32): z[i] = sum_n s1[n] conj(s2[n-(i-nlead)]), i = 0..nlag+nlead; complex64 out. */

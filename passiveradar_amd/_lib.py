@@ -97,7 +97,7 @@ TRACK_RECORD_DTYPE = np.dtype([("status", "<i4"), ("lifetime", "<i4"), ("measure
                                ("history", "u1", (20,)), ("overflow", "<i4")])
 
 
-MIN_LIB_VERSION = 610      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+MIN_LIB_VERSION = 620      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -141,6 +141,10 @@ _SIGNATURES = {
     "prc_nlms_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                    C.c_void_p]),
+    "prc_gal_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_gal_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                  C.c_void_p, C.c_void_p]),
     "prc_frontend_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(FrontendDesc)]),
     "prc_frontend_plan_destroy": (C.c_int, [C.c_void_p]),
     "prc_frontend_out_len": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

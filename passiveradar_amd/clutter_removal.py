@@ -1,9 +1,9 @@
 """Drop-in for the clutter filters of the reference's ``passiveRadar/clutter_removal.py`` that
 are on the north-star path: LS_Filter (:6-56), LS_Filter_Toeplitz (:109-160),
-LS_Filter_Multiple (:162-187), NLMS_filter (:189-249).  Same signatures, return dtypes and
-ValueError on mismatched inputs; the arithmetic runs in libprcore.so (complex64 streams,
-complex128 Levinson solve on device).  LS_Filter_SVD and GAL_JPE are not on the path
-(never called by the reference) and are deliberately absent.
+LS_Filter_Multiple (:162-187), NLMS_filter (:189-249), and GAL_JPE (:251-365).  Same signatures,
+return dtypes and ValueError on mismatched inputs; the arithmetic runs in libprcore.so (complex64
+streams, complex128 Levinson solve on device).  LS_Filter_SVD is not on the path (never called by
+the reference) and is deliberately absent.
 """
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib, engine
 
-__all__ = ["LS_Filter", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "NLMS_filter", "set_default_ls_method"]
+__all__ = ["LS_Filter", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "NLMS_filter", "GAL_JPE", "set_default_ls_method"]
 
 _LS_METHOD = {"m": 0}     # 0 auto | 1 time-domain kernels | 2 FFT kernels (tests flip it)
 
@@ -100,4 +100,45 @@ def NLMS_filter(refChannel, srvChannel, filterLen, mu, peek=10, initialTaps=None
     out = d_out.download((n,), np.complex64)
     if returnFilter:
         return out, d_tout.download((T,), np.complex64)
+    return out
+
+
+def _gal_check(refChannel, srvChannel, latticeLen, delayLineLen):
+    """the reference's argument errors (:294-303), raised before the library is touched"""
+    _check_same(refChannel, srvChannel)
+    if int(latticeLen) > int(delayLineLen):
+        raise ValueError("Delay line order must be greater than or equal to the lattice filter order")
+    if int(latticeLen) < 1:
+        # the reference fails on a NumPy broadcast error here (b[latticeLen:] = bo[latticeLen-1:-1])
+        raise ValueError(f"latticeLen must be at least 1, got {latticeLen}")
+
+
+def GAL_JPE(refChannel, srvChannel, latticeLen, delayLineLen, mu1, mu2, peek=10, return_filter=False):
+    """Gradient adaptive lattice joint-process estimator (:251-365), one wavefront per call on the GPU
+    (a workgroup beyond 2048 delay-line taps).  Inputs are cast to complex64, as NLMS_filter does; out,
+    and with ``return_filter`` the reflection coefficients k and transversal taps h (length
+    delayLineLen each), are complex64 like the reference's."""
+    _gal_check(refChannel, srvChannel, latticeLen, delayLineLen)
+    ref = np.ascontiguousarray(refChannel, dtype=np.complex64).reshape(-1)
+    srv = np.ascontiguousarray(srvChannel, dtype=np.complex64).reshape(-1)
+    n = ref.shape[0]
+    L, D = int(latticeLen), int(delayLineLen)
+    if n == 0:
+        out = np.zeros(0, np.complex64)
+        zk = np.zeros(D, np.complex64)
+        return (out, zk, zk.copy()) if return_filter else out
+    st = engine.staging()
+    d_ref = st.get("gal_ref", 8 * n)
+    d_srv = st.get("gal_srv", 8 * n)
+    d_out = st.get("gal_out", 8 * n)
+    d_k = st.get("gal_k", 8 * D) if return_filter else None
+    d_h = st.get("gal_h", 8 * D) if return_filter else None
+    wsb = engine.gal_workspace_bytes(D, 1)
+    d_ws = st.get("gal_ws", wsb) if wsb else None
+    d_ref.upload(ref)
+    d_srv.upload(srv)
+    engine.gal_execute(d_ref, d_srv, d_out, n, L, D, mu1, mu2, int(peek), d_k, d_h, 1, workspace=d_ws)
+    out = d_out.download((n,), np.complex64).reshape(np.shape(srvChannel))
+    if return_filter:
+        return out, d_k.download((D,), np.complex64), d_h.download((D,), np.complex64)
     return out

@@ -285,6 +285,23 @@ def nlms_execute(ref, srv, out, n, filter_len, mu, peek=10, taps_in=None, taps_o
                                  int(nstreams), stream))
 
 
+def gal_workspace_bytes(delay_len, nstreams=1):
+    """device bytes prc_gal_execute needs for ``nstreams`` streams of ``delay_len`` taps (0 up to 2048 taps)"""
+    nb = C.c_size_t(0)
+    check(lib().prc_gal_workspace_bytes(int(delay_len), int(nstreams), C.byref(nb)))
+    return int(nb.value)
+
+
+def gal_execute(ref, srv, out, n, lattice_len, delay_len, mu1, mu2, peek=10, k_out=None, h_out=None,
+                nstreams=1, stride=None, out_stride=None, workspace=None, stream=None):
+    """GAL_JPE over ``nstreams`` independent streams (device buffers or torch tensors); ``workspace``: a device buffer of
+    gal_workspace_bytes(delay_len, nstreams) bytes when that is non-zero.  ``stream``: the torch stream's handle."""
+    check(lib().prc_gal_execute(_ptr(ref), _ptr(srv), int(n), int(n if stride is None else stride), int(lattice_len),
+                                int(delay_len), int(peek), float(mu1), float(mu2), _ptr(out),
+                                int(n if out_stride is None else out_stride), _ptr(k_out), _ptr(h_out), int(nstreams),
+                                _ptr(workspace), stream))
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

@@ -382,10 +382,19 @@ class HipBackend:
     def __init__(self, cpi_samples, num_range_cells, num_doppler_cells, IF_sample_rate,
                  doppler_bins=(0, 1, -1, 2, -2), window=("kaiser", 5.0), clutter="ls",
                  batch=16, device=None, caf_method=0, doppler_method=0, nlms_mu=0.02, overlap=True,
-                 ls_method=0, nsub=1, ls_streams=3, nref=1, ls_reg=1.0, caf_multi="auto", caf_lanes=1):
+                 ls_method=0, nsub=1, ls_streams=3, nref=1, ls_reg=1.0, caf_multi="auto", caf_lanes=1,
+                 gal_lattice=8, gal_mu=(1e-3, 1e-2)):
         """clutter: "ls" = LS_Filter_Multiple over ``doppler_bins`` (main.py:169-176, the reference's choice),
         "ls_direct" = LS_Filter (clutter_removal.py:6-56: circular data matrix, ``ls_reg`` on the Gram diagonal, one
-        bin -- SURVEY 8's config-2 "LS_Filter variant"), "nlms" = NLMS_filter with step ``nlms_mu``, None = no canceller."""
+        bin -- SURVEY 8's config-2 "LS_Filter variant"), "nlms" = NLMS_filter with step ``nlms_mu``, "gal" = GAL_JPE
+        (clutter_removal.py:251-365) with ``gal_lattice`` reflection coefficients, a delay line of R taps and peek 10 (the
+        lengths "nlms" uses) and steps ``gal_mu`` = (mu1, mu2), None = no canceller.  The GAL defaults: (1e-3, 1e-2) are the
+        ballpark step sizes of the reference's docstring, and 8 reflection coefficients (at most 64 take the faster row
+        form of the kernel) are enough to whiten AR-like FM / OFDM spectra.  GAL restarts on every hop chunk, as the
+        reference's per-chunk filters do, and at these steps it does NOT converge within a chunk on strong clutter: on the
+        test scenes (clutter at 0 dB, targets at -40 dB) the zero-Doppler clutter stays the maximum of the map and the
+        targets sit at 0.5-1.2 % of it (5-17 % at mu2 = 0.1).  Use "ls" where the clutter must be removed; "gal" is the
+        reference's canceller made available.  Every chunk goes into one launch, one wavefront each, as for "nlms"."""
         import torch
         from . import engine
         from .range_doppler_processing import _named_window
@@ -396,7 +405,7 @@ class HipBackend:
         self.R, self.F = int(num_range_cells), int(num_doppler_cells)
         self.fs = float(IF_sample_rate)
         self.bins = tuple(float(b) for b in doppler_bins)
-        if clutter not in ("ls", "ls_direct", "nlms", None):
+        if clutter not in ("ls", "ls_direct", "nlms", "gal", None):
             raise ValueError(f"HipBackend: unknown clutter canceller {clutter!r}")
         self.clutter = clutter
         self.ls_like = clutter in ("ls", "ls_direct")       # block least-squares cancellers: plans, sub-batches, chains
@@ -404,6 +413,11 @@ class HipBackend:
         self.batch = int(batch)
         self.nref = max(1, int(nref))      # reference channels per surveillance channel (run_multi / frames_multi)
         self.nlms_mu = float(nlms_mu)
+        self.gal_lattice = int(gal_lattice)
+        self.gal_mu = (float(gal_mu[0]), float(gal_mu[1]))
+        if clutter == "gal" and not 1 <= self.gal_lattice <= self.R:
+            raise ValueError(f"HipBackend: gal_lattice must be in [1, {self.R}] (the delay line is R taps), got {gal_lattice}")
+        self._gal_ws = None
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # LS launches of batch/nsub chunks.  Measured on MI355X (config 2, two LS chains in flight): 256-chunk launches
         # (nsub = 1) 20.45 k frames/s, 128-chunk launches (nsub = 2) 19.56 k -- the latency-bound Durbin / solve kernels
@@ -542,6 +556,15 @@ class HipBackend:
         elif self.clutter == "ls_direct":
             (plan or self.ls).execute(ref_pad[off:], srv_pad[off:], out[off:], nb, C, C, self.fs, (0.0,), self.ls_reg,
                                       None, stream)
+        elif self.clutter == "gal":
+            wsb = self.engine.gal_workspace_bytes(self.R, nb)
+            ws = None
+            if wsb:
+                if self._gal_ws is None or self._gal_ws.numel() < wsb:
+                    self._gal_ws = self.torch.empty(wsb, dtype=self.torch.uint8, device=self.device)
+                ws = self._gal_ws
+            self.engine.gal_execute(ref_pad[off:], srv_pad[off:], out[off:], C, self.gal_lattice, self.R, self.gal_mu[0],
+                                    self.gal_mu[1], 10, None, None, nb, C, C, ws, stream)
         else:
             self.engine.nlms_execute(ref_pad[off:], srv_pad[off:], out[off:], C, self.R, self.nlms_mu, 10,
                                      None, None, nb, C, C, stream)
@@ -552,7 +575,7 @@ class HipBackend:
         if self.clutter is None:
             return srv_pad
         out = self._clean_target(srv_pad)
-        # NLMS is one wavefront per hop chunk and needs no plan workspace: every local chunk goes into ONE launch
+        # NLMS and GAL are one wavefront per hop chunk and need no plan workspace: every local chunk goes into ONE launch
         # (a 256-stream launch would leave three SIMDs in four idle); LS launches are bounded by the plan's workspace
         with self.torch.cuda.device(self.device):
             for c0, c1 in self._ls_ranges(nlocal):
