@@ -43,7 +43,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 620   /* 620: prc_gal_execute, prc_gal_workspace_bytes (GAL_JPE on device);
+#define PRC_VERSION 630   /* 630: prc_strack_desc, prc_strack_record, prc_strack_workspace_bytes, prc_strack_run
+                             (simple_target_tracker on device), prc_persistence (plotting_tools.persistence on device);
+                             620: prc_gal_execute, prc_gal_workspace_bytes (GAL_JPE on device);
                              610: prc_track_desc, prc_track_record, prc_track_plan_create / _destroy, prc_track_measure, prc_track_run
                              (get_measurements and multitarget_tracker on device);
                              600: every descriptor (prc_caf_desc, prc_ls_desc, prc_frontend_desc, prc_iir_desc) starts with `struct_size`,
@@ -469,6 +471,65 @@ int prc_track_measure(prc_track_plan* plan, const float* frames, int32_t nframes
  * start free (initialize_track(None)) at every call. */
 int prc_track_run(prc_track_plan* plan, const int32_t* counts, const prc_track_cand* cands, int32_t nframes,
                   prc_track_record* records, void* stream);
+
+/* ---- single-target tracker: target_detection.py:530-681 (simple_target_tracker) ------------------------------------ */
+/* Frames are [nframes][H][W] (H Doppler rows, W range columns), float32 (the CFAR output) or float64.  The result is the
+ * reference's on the frames as float64: per frame, v / mean|v| (whole frame), s = fliplr(frame.T), the masks s[:8, :],
+ * s[-8:, :], s[:, 250:260] (Python slice rules), the lock state's gate around the previous measurement_idx (slice
+ * normalisation, so a gate may wrap to empty), np.argmax(s * gate) with its NaN rule, then lock state and the adaptive
+ * Kalman update in fp64.  A float64 frame may differ only where the reference's own division merges two values within
+ * about one ulp (the kernels compare raw values).
+ * prc_strack_run enqueues two kernels on `stream`: a scan of every frame (several workgroups per frame, each frame read
+ * once) into `workspace`, then ONE workgroup that walks the frames in order, keeps the state on the device and reads only
+ * the gate window of a gated frame.  Neither allocates nor synchronises. */
+typedef enum prc_real_dtype { PRC_REAL_F32 = 0, PRC_REAL_F64 = 1 } prc_real_dtype;
+
+typedef struct prc_strack_desc {
+    uint32_t struct_size;  /* sizeof(prc_strack_desc) as the host compiled it (see Conventions)          */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                         */
+    int32_t H, W;          /* frame shape: Doppler rows, range columns (>= 1 each, H * W < 2^31)       */
+    int32_t dtype;         /* prc_real_dtype of the frames                                           */
+    int32_t reserved;      /* 0                                                                      */
+    double range_extent;   /* rangeExtent (km):   range   = range_extent * (1 - i0 / W)               */
+    double doppler_extent; /* dopplerExtent (Hz): doppler = doppler_extent * (2 * i1 / H - 1)         */
+} prc_strack_desc;
+#define PRC_STRACK_DESC_SIZE_630 40u
+
+/* the tracker's state after one frame (target_track_dtype_simple; range/doppler extents and F1, F2, Q, H, R are
+ * constants and not stored) */
+typedef struct prc_strack_record {
+    double lock_mode[4];        /* one-hot: 0 unlocked, 1 locking on, 2 locked, 3 losing lock             */
+    double measurement[2];      /* range (km), Doppler (Hz)                                               */
+    int64_t measurement_idx[2]; /* (range row, Doppler column) of s = fliplr(frame.T)                     */
+    double estimate[2];
+    double x[4];
+    double P[16];               /* row-major 4 x 4                                                        */
+    double S[4];                /* row-major 2 x 2                                                        */
+} prc_strack_record;
+#define PRC_STRACK_RECORD_SIZE 272u
+
+/* device bytes prc_strack_run needs in `workspace` for nframes frames of desc's shape */
+int prc_strack_workspace_bytes(const prc_strack_desc* desc, int32_t nframes, size_t* bytes);
+/* frames: DEVICE [nframes][H][W] of desc->dtype; state_in: DEVICE record to resume from (the last record of an earlier
+ * call), or NULL for the reference's initial state -- kept with its field-order quirk: measurement [30, -20],
+ * measurement_idx [35, -30], estimate [50, 50], lock_mode unlocked; records: DEVICE prc_strack_record [nframes];
+ * workspace: DEVICE, prc_strack_workspace_bytes bytes, not shared by calls in flight.  PRC_EINVAL for a bad descriptor,
+ * dtype or shape, nframes < 0 or a null pointer. */
+int prc_strack_run(const prc_strack_desc* desc, const void* frames, int32_t nframes, const prc_strack_record* state_in,
+                   prc_strack_record* records, void* workspace, void* stream);
+
+/* ---- persistence: plotting_tools.py persistence(X, k, hold, decay) ------------------------------------------------- */
+/* out[j] = sum_{i < n} frames[k - i] * decay**i for k = k_first + j, j < k_count, n = min(k + 1, hold), bitwise as the
+ * reference: the sum starts at +0.0 and adds the terms in order i = 0, 1, ..., each product and sum rounded on its own (no
+ * FMA); decay**i is the host libm pow(decay, i); a float32 frame gives the float32 product fl32(x * fl32(decay**i))
+ * (NumPy >= 2), widened and added in float64.  k < 0 or hold <= 0 give zeros.  frames: DEVICE [nframes][frame_elems] of
+ * in_dtype; out: DEVICE [k_count][frame_elems] of out_dtype (float32: the float64 sum rounded once).  The powers travel in
+ * the kernel arguments, 256 per launch; with more terms the launches chain through a float64 `out`, so a float32 out
+ * takes at most 256 terms.  Neither allocates nor synchronises.  PRC_EINVAL for bad dtypes, negative sizes, a null
+ * pointer, a frame k >= nframes that would be read, or more than 256 terms with a float32 out. */
+#define PRC_PERSISTENCE_TERMS_PER_LAUNCH 256
+int prc_persistence(const void* frames, int32_t in_dtype, int64_t frame_elems, int32_t nframes, int32_t k_first,
+                    int32_t k_count, int32_t hold, double decay, void* out, int32_t out_dtype, void* stream);
 
 #ifdef __cplusplus
 }

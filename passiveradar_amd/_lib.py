@@ -97,7 +97,26 @@ TRACK_RECORD_DTYPE = np.dtype([("status", "<i4"), ("lifetime", "<i4"), ("measure
                                ("history", "u1", (20,)), ("overflow", "<i4")])
 
 
-MIN_LIB_VERSION = 620      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+class StrackDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("H", C.c_int32), ("W", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
+                ("range_extent", C.c_double), ("doppler_extent", C.c_double)]
+
+
+class StrackRecord(C.Structure):
+    _fields_ = [("lock_mode", C.c_double * 4), ("measurement", C.c_double * 2), ("measurement_idx", C.c_int64 * 2),
+                ("estimate", C.c_double * 2), ("x", C.c_double * 4), ("P", C.c_double * 16), ("S", C.c_double * 4)]
+
+
+# NumPy view of prc_strack_record (same layout as the ctypes mirror)
+STRACK_RECORD_DTYPE = np.dtype([("lock_mode", "<f8", (4,)), ("measurement", "<f8", (2,)),
+                                ("measurement_idx", "<i8", (2,)), ("estimate", "<f8", (2,)), ("x", "<f8", (4,)),
+                                ("P", "<f8", (16,)), ("S", "<f8", (4,))])
+REAL_F32, REAL_F64 = 0, 1          # prc_real_dtype
+PERSISTENCE_TERMS_PER_LAUNCH = 256
+
+
+MIN_LIB_VERSION = 630      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -172,6 +191,11 @@ _SIGNATURES = {
     "prc_track_plan_destroy": (C.c_int, [C.c_void_p]),
     "prc_track_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_track_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "prc_strack_workspace_bytes": (C.c_int, [C.POINTER(StrackDesc), C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_strack_run": (C.c_int, [C.POINTER(StrackDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "prc_persistence": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_double, C.c_void_p, C.c_int32, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),

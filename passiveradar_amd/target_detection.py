@@ -1,7 +1,9 @@
 """Drop-ins for the reference's ``passiveRadar/target_detection.py``: ``CFAR_2D`` (:683-703), applied per frame to
-``|xambg|`` by range_doppler_plot.py:56-57 (SURVEY 8f "next" #3), and the multi-target Kalman tracker of
+``|xambg|`` by range_doppler_plot.py:56-57 (SURVEY 8f "next" #3), the multi-target Kalman tracker of
 multitarget_kalman_tracker.py: ``get_measurements`` (:164-229) and ``multitarget_tracker`` (:455-537), plus
-``track_maps``, that script's CFAR -> measure -> track chain (:44-63) in one device pass."""
+``track_maps``, that script's CFAR -> measure -> track chain (:44-63) in one device pass, and the single-target tracker
+of simple_kalman_tracker.py: ``simple_target_tracker`` (:626-681), plus ``simple_track_maps``, its CFAR -> track
+chain (:46-61)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +14,8 @@ from . import _lib, engine
 from ._lib import check, lib
 
 __all__ = ["CFAR_2D", "CFAR_2D_abs", "get_measurements", "multitarget_tracker", "track_maps",
-           "kalman_filter_dtype", "target_track_dtype"]
+           "kalman_filter_dtype", "target_track_dtype", "simple_target_tracker", "simple_track_maps",
+           "target_track_dtype_simple"]
 
 
 def CFAR_2D(X, fw, gw, thresh=None):
@@ -301,3 +304,131 @@ def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4):
         check(lib().prc_cfar2d(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
     m = _Measured(do.ptr, nframes, H, W, frame_extent, int(N_TRACKS), lambda name, nb: _lib.DeviceBuffer(nb), None)
     return _records_to_history(m.run(), int(N_TRACKS))
+
+
+# ---- single-target tracker (target_detection.py:530-681) ---------------------------------------------------------------
+target_track_dtype_simple = np.dtype([("lock_mode", np.float64, (4,)), ("measurement", np.float64, (2,)),
+                                      ("measurement_idx", np.int64, (2,)), ("estimate", np.float64, (2,)),
+                                      ("range_extent", np.float64), ("doppler_extent", np.float64),
+                                      ("kalman_state", kalman_filter_dtype)])
+# the constants of simple_target_tracker (:640-647) -- F1[1] and Q, R differ from multitarget_tracker's
+_SF1 = np.array([[1, 0, -0.003, 0], [0, 0, -0.003, -0.03], [0, 0, 1, 1], [0, 0, 0, 1]], dtype=np.float64)
+_SQ = np.diag([2.0, 0.02, 0.2, 0.05])
+_SR = np.diag([5.0, 5.0])
+
+
+def _strack_records_to_history(rec, range_extent, doppler_extent):
+    out = np.zeros(rec.shape, dtype=target_track_dtype_simple)
+    for k in ("lock_mode", "measurement", "measurement_idx", "estimate"):
+        out[k] = rec[k]
+    out["range_extent"] = range_extent
+    out["doppler_extent"] = doppler_extent
+    ks = out["kalman_state"]
+    ks["x"] = rec["x"]
+    ks["P"] = rec["P"].reshape(rec.shape + (4, 4))
+    ks["S"] = rec["S"].reshape(rec.shape + (2, 2))
+    ks["F1"], ks["F2"], ks["Q"], ks["H"], ks["R"] = _SF1, _F2, _SQ, _H, _SR
+    out["kalman_state"] = ks
+    return out
+
+
+def _strack_state_record(state):
+    """a history row (target_track_dtype_simple) as a prc_strack_record"""
+    row = np.asarray(state).reshape(-1)
+    if row.size != 1 or row.dtype.names is None:
+        raise ValueError("state= takes one row of a simple_target_tracker history")
+    row = row[0]
+    rec = np.zeros(1, dtype=_lib.STRACK_RECORD_DTYPE)
+    for k in ("lock_mode", "measurement", "measurement_idx", "estimate"):
+        rec[k] = row[k]
+    ks = row["kalman_state"]
+    rec["x"] = np.asarray(ks["x"]).reshape(4)
+    rec["P"] = np.asarray(ks["P"]).reshape(16)
+    rec["S"] = np.asarray(ks["S"]).reshape(4)
+    return rec
+
+
+def _strack_desc(H, W, dtype, range_extent, doppler_extent):
+    d = _lib.StrackDesc()
+    d.H, d.W, d.dtype = int(H), int(W), int(dtype)
+    d.range_extent, d.doppler_extent = float(range_extent), float(doppler_extent)
+    return d
+
+
+def _strack_run(frames_ptr, nframes, H, W, dtype, range_extent, doppler_extent, state, alloc, stream):
+    """prc_strack_run on device frames [nframes][H][W]; returns the records as STRACK_RECORD_DTYPE"""
+    d = _strack_desc(H, W, dtype, range_extent, doppler_extent)
+    nb = C.c_size_t(0)
+    check(lib().prc_strack_workspace_bytes(C.byref(d), int(nframes), C.byref(nb)))
+    ws = alloc(nb.value)
+    rec = alloc(_lib.STRACK_RECORD_DTYPE.itemsize * max(nframes, 1))
+    st_ptr = None
+    if state is not None:
+        st = _lib.DeviceBuffer(_lib.STRACK_RECORD_DTYPE.itemsize)
+        st.upload(_strack_state_record(state))
+        st_ptr = st.ptr
+    check(lib().prc_strack_run(C.byref(d), frames_ptr, int(nframes), st_ptr, rec.ptr, ws.ptr, stream))
+    out = rec.download(nframes, _lib.STRACK_RECORD_DTYPE, stream=stream)
+    return out
+
+
+def simple_target_tracker(data, rangeExtent, dopplerExtent, *, state=None):
+    """simple_target_tracker (target_detection.py:626-681): ``data`` is numpy (H Doppler, W range, Nframes) as the
+    reference takes it (float32 stays float32, anything else becomes float64), or a torch device tensor [N, H, W] of
+    float32 / float64.  Returns the reference's (Nframes,) history of target_track_dtype_simple, computed as the
+    reference does on the frames as float64 (a float64 frame may differ only where the reference's own division by the
+    frame mean merges two values within about one ulp).  ``state=`` (the one extension) is a history row -- the last
+    one of an earlier call -- to resume from; without it the track starts from the reference's initial state."""
+    if _lib.is_device_tensor(data):
+        import torch
+        t = data if data.dtype in (torch.float32, torch.float64) else data.to(torch.float64)
+        t = t.contiguous()
+        if t.dim() != 3:
+            raise ValueError("simple_target_tracker takes a device stack [N, H, W]")
+        N, H, W = t.shape
+        dt = _lib.REAL_F32 if t.dtype == torch.float32 else _lib.REAL_F64
+        with torch.cuda.device(t.device):
+            rec = _strack_run(t.data_ptr(), N, H, W, dt, rangeExtent, dopplerExtent, state,
+                              lambda nb: _TorchBuf(nb, t.device), _lib.torch_stream_ptr(t.device))
+        return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
+    d = np.asarray(data)
+    if d.ndim != 3:
+        raise ValueError("simple_target_tracker takes (H, W, Nframes) frames")
+    f = np.ascontiguousarray(np.moveaxis(d, 2, 0), dtype=np.float32 if d.dtype == np.float32 else np.float64)
+    N, H, W = f.shape
+    _lib.require_gpu()
+    dx = _lib.DeviceBuffer(f.nbytes)
+    dx.upload(f)
+    rec = _strack_run(dx.ptr, N, H, W, _lib.REAL_F32 if f.dtype == np.float32 else _lib.REAL_F64, rangeExtent,
+                      dopplerExtent, state, lambda nb: _lib.DeviceBuffer(nb), None)
+    return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
+
+
+def simple_track_maps(xambg, rangeExtent, dopplerExtent, fw=18, gw=4):
+    """simple_kalman_tracker.py:46-61 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per frame
+    (CFAR_2D_abs; CFAR_2D for a real magnitude stack) -> simple_target_tracker on the float32 CFAR maps.  ``xambg`` is
+    a torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it."""
+    if _lib.is_device_tensor(xambg):
+        cf = CFAR_2D_abs(xambg, fw, gw) if xambg.is_complex() else CFAR_2D(xambg, fw, gw)
+        if cf.dim() == 2:
+            cf = cf.unsqueeze(0)
+        return simple_target_tracker(cf, rangeExtent, dopplerExtent)
+    x = np.moveaxis(np.asarray(xambg), 2, 0)
+    _lib.require_gpu()
+    if np.iscomplexobj(x):
+        xc = np.ascontiguousarray(x, dtype=np.complex64)
+        nframes, H, W = xc.shape
+        dx = _lib.DeviceBuffer(xc.nbytes)
+        dx.upload(xc)
+        do = _lib.DeviceBuffer(nframes * H * W * 4)
+        check(lib().prc_cfar2d_c64(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    else:
+        xf = np.ascontiguousarray(x, dtype=np.float32)
+        nframes, H, W = xf.shape
+        dx = _lib.DeviceBuffer(xf.nbytes)
+        dx.upload(xf)
+        do = _lib.DeviceBuffer(xf.nbytes)
+        check(lib().prc_cfar2d(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    rec = _strack_run(do.ptr, nframes, H, W, _lib.REAL_F32, rangeExtent, dopplerExtent, None,
+                      lambda nb: _lib.DeviceBuffer(nb), None)
+    return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
