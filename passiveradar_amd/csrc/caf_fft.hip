@@ -137,11 +137,6 @@ __global__ __launch_bounds__(64 * CAFF_WAVES, NLB == 1 ? CAFF_OCC : 2) void caf_
         float tn[HAS_TAPS ? 16 : 1];
         // nz: registers r >= nz lie beyond the piece for every lane (64 r >= cnt): not loaded, zero
         auto issue_u = [&](int n0, int nz = 16) {
-#ifdef CAFF_EXP_NOLOAD      // timing ablation only (wrong results): no global loads
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { un[r] = make_float2((float)(lane + n0), (float)r); wn[r] = 0.5f; }
-            return;
-#endif
             const int rem = hi - n0 + 1;
             int cnt = rem < B ? rem : B;
             if (NV - n0 < cnt) cnt = NV - n0;
@@ -152,11 +147,7 @@ __global__ __launch_bounds__(64 * CAFF_WAVES, NLB == 1 ? CAFF_OCC : 2) void caf_
                 else un[r] = make_float2(0.f, 0.f);
             }
             if (HAS_WIN) {
-#ifdef CAFF_EXP_WINSMALL              // timing ablation, never shipped (wrong results): the window read out of its first 8 KB only --
-                const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + (n0 & 1023), clampu(cnt) * 4u);   // what its 4 N bytes per frame cost
-#else
                 const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, clampu(cnt) * 4u);
-#endif
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     if (r < 8 || (r < 12 && nz > 8) || nz > 12) wn[r] = prc_buf_load_f32(rw, vo4, 256u * r);
@@ -177,11 +168,6 @@ __global__ __launch_bounds__(64 * CAFF_WAVES, NLB == 1 ? CAFF_OCC : 2) void caf_
         constexpr bool WEIGHTED = HAS_WIN || HAS_TAPS;
         // srv slots [0, cnt+LB-1) of lag block lb: frame offsets start .. with circular wrap (:82)
         auto issue_v = [&](float2 (&v)[16], int n0, int cnt, int lb) {
-#ifdef CAFF_EXP_NOLOAD
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = make_float2((float)(lane - n0), (float)(r + cnt + lb));
-            return;
-#endif
             int start = n0 + lb * LB;
             if (start >= N) start -= N;
             const int want = cnt + LB - 1;

@@ -20,7 +20,6 @@
 #endif
 #ifndef CAFT_WAVES_PER_SIMD
 #define CAFT_WAVES_PER_SIMD 3
-#define CAFT_NO_PREFETCH 1
 #endif
 #include "caf_internal.h"
 #include "fft_team.h"
@@ -62,10 +61,6 @@ int ft_device_tables(const float2** out) {
     return PRC_OK;
 }
 
-
-#ifndef CAFT_WAVES_PER_SIMD
-#define CAFT_WAVES_PER_SIMD 2
-#endif
 template <bool HAS_WIN>
 __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_kernel(CafTeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -126,26 +121,15 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
         const int hi_f = hi - tail;                            // last sample that goes through the transforms
 
         for (int lb = 0; lb < a.nlagblk; ++lb) {
-#ifdef CAFT_EXP_NOACC           // timing ablation, never shipped (wrong results): the accumulator shares the registers of the
-            float2 v[16];       // surveillance spectrum -- what the kernel would run like if its state were 64 VGPRs, not 96
-            float2(&acc)[16] = v;
-#else
             float2 acc[16];
 #pragma unroll
             for (int m = 0; m < 16; ++m) acc[m] = make_float2(0.f, 0.f);
-#endif
 
-            // Software pipeline as in caf_fft.hip: raw buffer loads issued one transform ahead of their use; the
-            // descriptor's num_records encodes "samples of this piece that exist" (zero padding of U, ragged
-            // last piece, n_valid < n, the prefetch past the last piece).
+            // Raw buffer loads as in caf_fft.hip: the descriptor's num_records encodes "samples of this piece that
+            // exist" (zero padding of U, ragged last piece, n_valid < n).
             float2 un[16];
             float wn[16];
             auto issue_u = [&](int n0, int nz = 16) {
-#ifdef CAFT_EXP_NOLOAD
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { un[r] = make_float2((float)(t + n0), (float)r); wn[r] = 0.5f; }
-                return;
-#endif
                 const int rem = hi_f - n0 + 1;
                 int cnt = rem < B ? rem : B;
                 if (NV - n0 < cnt) cnt = NV - n0;
@@ -167,11 +151,6 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
             };
             // srv slots [0, cnt+LB-1) of this lag block: frame offsets start .. with circular wrap (:82)
             auto issue_v = [&](float2 (&v)[16], int n0, int cnt) {
-#ifdef CAFT_EXP_NOLOAD
-#pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = make_float2((float)(t - n0), (float)(r + cnt));
-                return;
-#endif
                 int start = n0 + lb * LB;
                 if (start >= N) start -= N;
                 const int want = cnt + LB - 1;
@@ -193,34 +172,13 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
                     }
                 }
             };
-#ifndef CAFT_NO_PREFETCH
-            issue_u(lo);
-            for (int n0 = lo; n0 <= hi_f; n0 += B) {
-                const int rem = hi_f - n0 + 1;
-                const int cnt = rem < B ? rem : B;
-                float2 u[16], v[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    u[r] = HAS_WIN ? make_float2(un[r].x * wn[r], un[r].y * wn[r]) : un[r];
-                issue_v(v, n0, cnt);
-                __builtin_amdgcn_sched_barrier(0);
-                ft4096_fwd<0>(u, f);
-                __builtin_amdgcn_sched_barrier(0);
-                issue_u(n0 + B);                                // past the last piece: zero records -> zeros
-                __builtin_amdgcn_sched_barrier(0);
-                ft4096_fwd<1>(v, f);
-#else
             // high-occupancy form: nothing is loaded a piece ahead (the other wavefronts of the SIMD cover the latency);
             // only u, v and the accumulator are ever live together, and the surveillance loads of a piece are issued
             // before the reference transform so that they fly under it (round 3, -2 %)
             for (int n0 = lo; n0 <= hi_f; n0 += B) {
                 const int rem = hi_f - n0 + 1;
                 const int cnt = rem < B ? rem : B;
-#ifdef CAFT_EXP_NOACC
-                float2 u[16];
-#else
                 float2 u[16], v[16];
-#endif
                 // zero-padded reference piece: a piece of at most 2048 (3072) samples leaves registers 8..15 (12..15) of
                 // every thread zero -- their loads, window products and first-pass additions are skipped (uniform branch)
                 const int nz = cnt <= 2048 ? 8 : (cnt <= 3072 ? 12 : 16);
@@ -251,7 +209,6 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 ft4096_fwd<1>(v, f);
-#endif
 #pragma unroll
                 for (int m = 0; m < 16; ++m) cmac_conj_a(acc[m], u[m], v[m]);
             }

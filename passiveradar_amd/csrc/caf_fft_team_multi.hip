@@ -108,11 +108,7 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_MULTI_WAVES) void caf_fft_team_mul
             // pieces of at most 2048 samples (config 5) are loaded one transform ahead (24 VGPRs in flight); longer ones
             // (config 3's 3072-sample piece is 36) would spill next to V0, V1, the accumulator and the piece in work, and
             // are loaded where they are used
-#ifdef CAFT_MULTI_NO_AHEAD
-            constexpr bool AHEAD = false;
-#else
             constexpr bool AHEAD = NZM <= 8;
-#endif
             float2 un[NZM];
             float wn[NZM];
             auto issue_u = [&](auto nzc, const float2* __restrict__ ref, int n0, int cnt) {

@@ -43,12 +43,7 @@
 #ifndef FT_NBUF
 #define FT_NBUF 2                       // exchange buffers: 2 = one barrier per forward transform; 1 = two barriers, half the LDS
 #endif
-#ifdef FT_TW2_LDS
-#define FT_TW2_ELEMS FT_P               // the 16 T2 constants of every thread live in LDS ([k2][t], 32 KB) instead of 32 VGPRs:
-#else                                   // for kernels held at two wavefronts per SIMD anyway (80 KB of LDS each)
-#define FT_TW2_ELEMS 0
-#endif
-#define FT_LDS_ELEMS (FT_TW1 + FT_NBUF * FT_BUF + FT_TW2_ELEMS)   // float2 elements of LDS per workgroup (71 680 B with two buffers)
+#define FT_LDS_ELEMS (FT_TW1 + FT_NBUF * FT_BUF)   // float2 elements of LDS per workgroup (71 680 B with two buffers)
 #define FT_GTAB (FT_TW1 + FT_P)         // global table: TW1 then W_4096^m, m = 0..4095
 
 struct FtLane {
@@ -57,9 +52,7 @@ struct FtLane {
     float2* wr;         // exchange base + 17 t           : write (t, rho) at wr[rho]            (+ FT_BUF for buffer 1)
     const float2* rdA;  // exchange base + 272 hi + lo    : row-private read (16 hi + m, lo) at rdA[17 m]
     const float2* rdB;  // exchange base + 17 lo + hi     : cross-wave read (16 m + lo, hi) at rdB[272 m]
-#if defined(FT_TW2_LDS)
-    const float2* tw2l; // lds + FT_TW1 + FT_NBUF FT_BUF + t : W_4096^(lo (hi + 16 k2)) at tw2l[256 k2]
-#elif defined(FT_TW2_FACTORED)
+#if defined(FT_TW2_FACTORED)
     float2 tw2b;        // W_4096^(lo hi); the k2 part W_256^(lo k2) comes from the TW1 table (tw2t[16 k2])
     const float2* tw2t; // lds + lo
 #else
@@ -69,9 +62,7 @@ struct FtLane {
 
 // T2 twiddle of register k2 (forward sense; the inverse multiplies by its conjugate)
 __device__ __forceinline__ float2 ft_tw2(const FtLane& f, int k2) {
-#if defined(FT_TW2_LDS)
-    return f.tw2l[FT_THREADS * k2];
-#elif defined(FT_TW2_FACTORED)
+#if defined(FT_TW2_FACTORED)
     return k2 == 0 ? f.tw2b : cmul(f.tw2b, f.tw2t[16 * k2]);
 #else
     return f.tw2[k2];
@@ -90,14 +81,7 @@ __device__ __forceinline__ FtLane ft_setup(float2* lds, const float2* __restrict
     f.rdA = x + 16 * FT_PITCH * hi + lo;
     f.rdB = x + FT_PITCH * lo + hi;
     lds[f.t] = gtab[f.t];               // FT_TW1 == FT_THREADS
-#if defined(FT_TW2_LDS)
-    {
-        float2* tl = lds + FT_TW1 + FT_NBUF * FT_BUF + f.t;
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) tl[FT_THREADS * k2] = gtab[FT_TW1 + ((lo * (hi + 16 * k2)) & (FT_P - 1))];
-        f.tw2l = tl;
-    }
-#elif defined(FT_TW2_FACTORED)
+#if defined(FT_TW2_FACTORED)
     f.tw2b = gtab[FT_TW1 + lo * hi];
     f.tw2t = lds + lo;
 #else
@@ -108,12 +92,7 @@ __device__ __forceinline__ FtLane ft_setup(float2* lds, const float2* __restrict
     return f;
 }
 
-#ifdef FT_EXP_NOBARRIER          // timing ablation only (wrong results)
-#define FT_BARRIER() ((void)0)
-#endif
-#ifndef FT_BARRIER
 #define FT_BARRIER() __syncthreads()
-#endif
 __device__ __forceinline__ void ft_team_sync() { FT_BARRIER(); }
 
 // Forward FFT: time layout -> frequency layout.  CUR: buffer of the cross-wave exchange (alternate 0, 1, 0, ...).
@@ -125,25 +104,21 @@ __device__ __forceinline__ void ft4096_fwd(float2 (&x)[16], const FtLane& f) {
     dft16<1, NZ>(x);
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) x[k1] = mul_tw<1>(x[k1], f.tw1[16 * k1]);
-#ifndef FT_EXP_NOX1
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) f.wr[T + k1] = x[k1];
     FT_BARRIER();
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = f.rdB[T + 16 * FT_PITCH * m];
     if (FT_NBUF == 1) FT_BARRIER();       // single buffer: every cross-wave read phase is closed by a barrier
-#endif
     dft16<1>(x);
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) x[k2] = mul_tw<1>(x[k2], ft_tw2(f, k2));
-#ifndef FT_EXP_NOX2
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) f.wr[O + k2] = x[k2];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < 16; ++j) x[j] = f.rdA[O + FT_PITCH * j];
     __builtin_amdgcn_wave_barrier();
-#endif
     dft16<1>(x);
 }
 #else
@@ -156,24 +131,20 @@ __device__ __forceinline__ void ft4096_fwd(float2 (&xs)[16], const FtLane& f) {
     for (int r = 0; r < 16; ++r) x[r] = pk_from(xs[r]);
     pk_dft16<1, NZ>(x);
     pk_twiddle<1, 1>(x, [&](int k1) { return pk_from(f.tw1[16 * k1]); });
-#ifndef FT_EXP_NOX1
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) f.wr[T + k1] = pk_to(x[k1]);
     FT_BARRIER();
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = pk_from(f.rdB[T + 16 * FT_PITCH * m]);
     if (FT_NBUF == 1) FT_BARRIER();
-#endif
     pk_dft16<1>(x);
     pk_twiddle<1, 0>(x, [&](int k2) { return pk_from(ft_tw2(f, k2)); });
-#ifndef FT_EXP_NOX2
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) f.wr[O + k2] = pk_to(x[k2]);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < 16; ++j) x[j] = pk_from(f.rdA[O + FT_PITCH * j]);
     __builtin_amdgcn_wave_barrier();
-#endif
     pk_dft16<1>(x);
 #pragma unroll
     for (int r = 0; r < 16; ++r) xs[r] = pk_to(x[r]);
@@ -187,25 +158,21 @@ __device__ __forceinline__ void ft4096_inv(float2 (&x)[16], const FtLane& f) {
     constexpr int T = (FT_NBUF == 2 ? CUR : 0) * FT_BUF;
     if (FT_NBUF == 2) FT_BARRIER();       // the buffer must be quiet before the row-private exchange below
     dft16<-1>(x);
-#ifndef FT_EXP_NOX2
 #pragma unroll
     for (int j = 0; j < 16; ++j) f.wr[T + j] = x[j];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = f.rdA[T + FT_PITCH * m];
     __builtin_amdgcn_wave_barrier();
-#endif
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) x[k2] = mul_tw<-1>(x[k2], ft_tw2(f, k2));
     dft16<-1>(x);
-#ifndef FT_EXP_NOX1
 #pragma unroll
     for (int m = 0; m < 16; ++m) f.wr[T + m] = x[m];
     FT_BARRIER();
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) x[k1] = f.rdB[T + 16 * FT_PITCH * k1];
     if (FT_NBUF == 1) FT_BARRIER();
-#endif
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) x[k1] = mul_tw<-1>(x[k1], f.tw1[16 * k1]);
     dft16<-1>(x);
@@ -219,24 +186,20 @@ __device__ __forceinline__ void ft4096_inv(float2 (&xs)[16], const FtLane& f) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) x[r] = pk_from(xs[r]);
     pk_dft16<-1>(x);
-#ifndef FT_EXP_NOX2
 #pragma unroll
     for (int j = 0; j < 16; ++j) f.wr[T + j] = pk_to(x[j]);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = pk_from(f.rdA[T + FT_PITCH * m]);
     __builtin_amdgcn_wave_barrier();
-#endif
     pk_twiddle<-1, 0>(x, [&](int k2) { return pk_from(ft_tw2(f, k2)); });
     pk_dft16<-1>(x);
-#ifndef FT_EXP_NOX1
 #pragma unroll
     for (int m = 0; m < 16; ++m) f.wr[T + m] = pk_to(x[m]);
     FT_BARRIER();
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) x[k1] = pk_from(f.rdB[T + 16 * FT_PITCH * k1]);
     if (FT_NBUF == 1) FT_BARRIER();
-#endif
     pk_twiddle<-1, 1>(x, [&](int k1) { return pk_from(f.tw1[16 * k1]); });
     pk_dft16<-1>(x);
 #pragma unroll

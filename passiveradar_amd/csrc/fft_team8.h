@@ -132,11 +132,7 @@ __device__ __forceinline__ void pk_twiddle8_s(v2f (&x)[8], const v2f (&c)[8]) {
     }
 }
 
-#ifdef F8_EXP_NOBARRIER          // timing ablation only (wrong results)
-#define F8_BARRIER() ((void)0)
-#else
 #define F8_BARRIER() __syncthreads()
-#endif
 
 // Forward FFT: time layout -> frequency layout.  NZ: registers x[NZ..7] are zero in every thread (a zero-padded piece of
 // at most 512 NZ samples).

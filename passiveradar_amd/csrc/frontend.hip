@@ -325,11 +325,7 @@ __device__ __forceinline__ void feg_stage_interior(const FeArgs& a, const FegArg
     // per thread (round 6): left to the general form below they cost every workgroup a second round trip to memory and
     // eight rotations on its first wavefront alone, with the other seven waiting at the barrier.
     const int rem = g.span - nfull * (FEG_THREADS * FEG_CHUNK);
-#ifdef FEG_EXP_TAIL_GENERAL        // the form of rounds 4-5, for A/B runs
-    const bool fold = false;
-#else
     const bool fold = nfull > 0 && rem > 0 && rem <= FEG_THREADS;
-#endif
     int k0 = tid;
     for (int trip = 0; trip < nfull; ++trip, k0 += FEG_THREADS * FEG_CHUNK) {
         float2 v[NCH][FEG_CHUNK];
@@ -344,11 +340,7 @@ __device__ __forceinline__ void feg_stage_interior(const FeArgs& a, const FegArg
         for (int c = 0; c < FEG_CHUNK; ++c) {
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
-#ifdef FEG_EXP_NOLOAD                 // timing ablation, never shipped: the staging without its global loads
-                v[ch][c] = make_float2((float)(k0 + c), (float)ch);
-#else
                 v[ch][c] = fe_load<SRC>(raw[ch], i_w + k0 + c * FEG_THREADS);
-#endif
             }
         }
         // the loads first, then everything that does not need them (the phases: most of the work) while they are in flight --
@@ -358,10 +350,6 @@ __device__ __forceinline__ void feg_stage_interior(const FeArgs& a, const FegArg
         for (int c = 0; c < FEG_CHUNK; ++c) {
             const int k = k0 + c * FEG_THREADS;
             const int at = feg_at<PAD>(a, g, k);
-#ifdef FEG_EXP_NOROT                  // timing ablation, never shipped: the staging without its rotations
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) X[ch * g.xstride + at] = v[ch][c];
-#else
             if (MIX) {
                 const v2f tw = fe_twiddle(a, i_w + k, blk_phase);      // ONE rotation factor for every channel of the block
 #pragma unroll
@@ -370,7 +358,6 @@ __device__ __forceinline__ void feg_stage_interior(const FeArgs& a, const FegArg
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) X[ch * g.xstride + at] = v[ch][c];
             }
-#endif
         }
         if (extra) {
             const int at = feg_at<PAD>(a, g, kx);
@@ -425,11 +412,6 @@ __device__ __forceinline__ void feg_trips(const FeArgs& a, const FegArgs& g, con
     // (two register sets in turn, explicit lgkmcnt(0) waits) changes nothing, before and after the scalar work below was
     // removed, and neither does dealing the rows out by cost with narrower column windows in the table's corners
     // (PRC_OPT_FE_BALANCE: 37 % fewer multiply-adds), nor does a loop of four rows per iteration.
-#ifdef FEG_EXP_SAMEROW                    // timing ablation, never shipped: every trip reads the same two tap rows (128 bytes of table)
-#define FEG_TR_STEP 0
-#else
-#define FEG_TR_STEP 32
-#endif
     // Taps as SGPR PAIRS (round 5).  A packed multiply-add takes a 64-bit scalar source and op_sel / op_sel_hi say which
     // half feeds each half of the result: the tap in the LOW half of a pair serves with op_sel_hi:[0,..], the one in the HIGH
     // half with op_sel:[1,..] op_sel_hi:[1,..] -- two adjacent taps of a row are one aligned pair as s_load delivers them.
@@ -462,7 +444,7 @@ __device__ __forceinline__ void feg_trips(const FeArgs& a, const FegArgs& g, con
             pa[j] = tp[(Q0 >> 1) + j];
             pb[j] = tp[8 + (Q0 >> 1) + j];
         }
-        tr += FEG_TR_STEP;
+        tr += 32;
         const int off0 = next_off(), off1 = next_off();
         x0 = xl[off0];
         x1 = xl[off1];
@@ -572,17 +554,8 @@ __global__ __launch_bounds__(FEG_THREADS, 2 * FEG_WAVES / 4) void frontend_group
         raw[NCH - 1] = fe_block<FE_SRC_RT>(a2, b);
     }
     const double blk_phase = fe_block_phase(a, b);
-#ifdef FEG_EXP_STAGGER              // A/B, never shipped (round 6: 7.1-7.3 us per block-channel with 3 / 7 / 10 us of delay, 7.0-7.3 without):
-    {                               // the second workgroup of every CU in the first dispatch round starts late, so that the two
-                                    // workgroups of a CU are in different phases (staging against row loop) from then on
-        const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
-        if (lin >= 256u && lin < 512u)
-            for (int i = 0; i < FEG_EXP_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);
-    }
-#endif
     const int64_t N0 = (int64_t)blockIdx.x * G;                     // first group of the workgroup
     const int64_t i_w = N0 * a.dn + g.r_first;                      // input index of the window's first sample
-#ifndef FEG_EXP_NOSTAGE              // timing ablation, never shipped: no staging at all (the row loop reads whatever LDS holds)
     switch (a.src) {            // one scalar branch per window, not per sample
         case PRC_RAW_I8: feg_stage<PRC_RAW_I8, NCH>(a, g, X, raw, i_w, blk_phase, tid); break;
         case PRC_RAW_U8: feg_stage<PRC_RAW_U8, NCH>(a, g, X, raw, i_w, blk_phase, tid); break;
@@ -590,15 +563,11 @@ __global__ __launch_bounds__(FEG_THREADS, 2 * FEG_WAVES / 4) void frontend_group
         case PRC_RAW_F32: feg_stage<PRC_RAW_F32, NCH>(a, g, X, raw, i_w, blk_phase, tid); break;
         default: feg_stage<PRC_RAW_C64, NCH>(a, g, X, raw, i_w, blk_phase, tid);
     }
-#endif
     __syncthreads();
     const float2* xl = NCH == 2 ? X + (lane >> 5) * g.xstride + (lane & 31) * g.lane_stride : X + lane * g.lane_stride;
     v2f acc[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) acc[q] = v2f{0.f, 0.f};
-#ifdef FEG_EXP_NOFIR                      // timing ablation, never shipped: one trip
-    feg_trips<0, NQ, NQ, false>(a, g, xl, 0, 1, acc);
-#else
     if (g.fold_M > 0) {
 #pragma unroll 1
         for (int sgm = 0; sgm < FEG_SEGS; ++sgm) {
@@ -616,16 +585,6 @@ __global__ __launch_bounds__(FEG_THREADS, 2 * FEG_WAVES / 4) void frontend_group
                                __builtin_amdgcn_readfirstlane((int)g.seg_code[w][sgm]), acc);
         }
     }
-#endif
-#ifdef FEG_EXP_NOEPI                  // timing ablation, never shipped: every wavefront stores its own partial sums, nothing is added up
-    {
-        float2* out = a.out + (int64_t)b * a.out_stride;
-        const int64_t m = N0 * a.up + (int64_t)(lane & (G - 1)) * a.up;
-        if (w == 0 && m + NQ <= a.n_out)
-            for (int q = 0; q < NQ; ++q) out[m + q] = make_float2(acc[q].x, acc[q].y);
-        return;
-    }
-#endif
     __syncthreads();                                                // the window is dead: its LDS takes the partial sums
     // [wave][lane][q] at an odd pitch: a lane's `up` sums are stored pitch samples from its neighbour's (b64 stores,
     // conflict-free for an odd pitch) and read back as what they are, consecutive outputs ([wave][q][lane] measured 68 %
@@ -838,9 +797,6 @@ extern "C" int prc_frontend_plan_create(prc_frontend_plan** plan, const prc_fron
                     for (int64_t q = 0; q < q0; ++q)
                         if (has(rho, q)) ok = false;
                     q0s[(size_t)rho] = q0;
-#ifdef FEG_EXP_FOLD_ONESEG                 // timing ablation, never shipped (wrong results): every folded row as a one-input row, so that
-                    q0s[(size_t)rho] = 0; //   a wavefront's rows are ONE segment -- what the segment switches cost
-#endif
                 }
                 // equal runs of folded rows per wavefront; inside a run, consecutive rows with the same q0 form a segment
                 int16_t f_row0[FEG_WAVES][FEG_SEGS] = {}, f_rows[FEG_WAVES][FEG_SEGS] = {}, f_q0[FEG_WAVES][FEG_SEGS] = {};
@@ -941,12 +897,6 @@ static int frontend_run(prc_frontend_plan* p, const void* raw, const void* raw2,
     a.taps = p->d_taps;
     a.phases = nullptr;
     a.ph_n = 0;
-#ifdef FE_EXP_PHASES_DIRECT     // the form of rounds 3-5, kept for A/B runs only: asynchronous copy straight from the caller's array
-    if (mix && phases_host) {
-        PRC_HIP(hipMemcpyAsync(p->d_phases, phases_host, sizeof(double) * nblocks, hipMemcpyHostToDevice, stream));
-        a.phases = p->d_phases;
-    }
-#else
     if (mix && phases_host) {
         if (nblocks <= FE_PH_INLINE) {
             memcpy(a.ph_inline, phases_host, sizeof(double) * nblocks);
@@ -962,7 +912,6 @@ static int frontend_run(prc_frontend_plan* p, const void* raw, const void* raw2,
             a.phases = p->d_phases;
         }
     }
-#endif
     a.raw_stride = raw_stride;
     a.out_stride = out_stride;
     a.n_in = p->n_in;

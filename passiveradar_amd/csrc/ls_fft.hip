@@ -623,7 +623,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_corr_cached_kernel(LsFft
 // block + L2-served overlap, one more FFT): fewer HBM bytes but a third transform, which makes the kernel
 // VALU-bound -- measured slower than the HBM-bound cached form.
 #ifndef LSF_FUSED_OCC
-#define LSF_FUSED_OCC 2      // wavefronts per SIMD (A/B builds: with the transforms ablated, 3 tells whether more loads in flight help)
+#define LSF_FUSED_OCC 2      // wavefronts per SIMD (A/B builds override it: 3 tells whether more loads in flight help)
 #endif
 template <bool CACHED, bool ROT_IN>
 __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached_kernel(LsFftArgs a) {
@@ -676,11 +676,6 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
     auto issue_x = [&](int p) {
         const bool live = p < nblocks;
         if (CACHED) {
-#ifdef LSF_EXP_NOLOAD       // timing ablation only (wrong results): no global loads
-#pragma unroll
-            for (int r = 0; r < 16; ++r) xn[r] = make_float2((float)(lane + p), (float)r);
-            return;
-#endif
             const __amdgpu_buffer_rsrc_t rc = prc_rsrc(cache + (int64_t)(live ? p : 0) * FFTW_P,
                                                        live ? FFTW_P * 8u : 0u);
             // cache layout [register pair m][lane][2]: registers 2m, 2m+1 of a lane are 16 contiguous bytes (1 KB per
@@ -725,14 +720,9 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
         __builtin_amdgcn_sched_barrier(0);
         issue_x(p + nwaves);
         {
-#ifdef LSF_EXP_NOLOAD
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] = make_float2((float)(lane - n0), (float)(r + cnt));
-#else
             const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, lsf_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) sv[r] = prc_buf_load_c64(rs, vslot + 512u * r, 0u);
-#endif
         }
         // one rotation on the way out: from this bin's frame to the frame of whoever reads the stream next
         const bool rot_out = a.rot || a.rot2;
@@ -746,9 +736,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
             if (ROT_IN) ibase = make_float2(p1.x, -p1.y);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifndef LSF_EXP_NOFFT       // timing ablation only (wrong results): no transforms, the memory pattern alone
         fft1024_inv<true>(y, tile, tab, f);
-#endif
         // last `peek` outputs of the block: rho samples whose ramp restarted carry gamma instead of 1
         if (a.rot && peek > 0 && n0 + cnt > n - peek) {
             const float2 g1 = a.gamma_m1;
@@ -790,9 +778,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
             y[r] = in ? o : make_float2(0.f, 0.f);
         }
         if (a.has_next) {
-#ifndef LSF_EXP_NOFFT
             fft1024_fwd(y, tile, tab, f);
-#endif
 #pragma unroll
             for (int m = 0; m < 16; ++m) cmac_bconj(wrs[m], y[m], xc[m]);
         }

@@ -44,22 +44,13 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
     float2 xn[16];
     auto issue_x = [&](int p) {
         const bool live = p < nblocks;
-#ifdef LTC_EXP_NOLOAD       // timing ablation only (wrong results): no global loads
-#pragma unroll
-        for (int r = 0; r < 16; ++r) xn[r] = make_float2((float)(t + p), (float)r);
-        return;
-#endif
         const __amdgpu_buffer_rsrc_t rc = prc_rsrc(cache + (int64_t)(live ? p : 0) * FT_P, live ? FT_P * 8u : 0u);
 #pragma unroll
         for (int m = 0; m < 8; ++m) prc_buf_load_2c64(rc, (unsigned)t * 16u, 4096u * m, xn[2 * m], xn[2 * m + 1]);
     };
     // a contiguous run of pieces per team (stream4.hip: +3 % over pieces team, team + nteams, ...)
-#ifdef LTC_STRIDED
-    const int p0 = team, pstep = nteams, pend = nblocks;
-#else
     const int per = (nblocks + nteams - 1) / nteams;
-    const int p0 = team * per, pstep = 1, pend = p0 + per < nblocks ? p0 + per : nblocks;
-#endif
+    const int p0 = team * per, pend = p0 + per < nblocks ? p0 + per : nblocks;
     issue_x(p0 < pend ? p0 : nblocks);                        // flies under the transform of the taps
 
     // H~ = FFT(taps) / 4096 of this block (frequency layout); element (r, t) is private to thread t and parked in LDS
@@ -83,7 +74,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
     for (int m = 0; m < 16; ++m) wrs[m] = make_float2(0.f, 0.f);
 
     ltc_loads_landed();
-    for (int p = p0; p < pend; p += pstep) {
+    for (int p = p0; p < pend; ++p) {
         const int n0 = p * B;
         const int cnt = (n - n0) < B ? (n - n0) : B;
         float2 xc[16], y[16], sv[16];
@@ -92,18 +83,10 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
 #pragma unroll
         for (int r = 0; r < 16; ++r) y[r] = cmul(xc[r], Hs[FT_THREADS * r]);
         __builtin_amdgcn_sched_barrier(0);
-#ifdef LTC_EARLY_PREFETCH    // A/B: the next block's loads issued before the inverse transform (32 more VGPRs live through it)
-        issue_x(p + pstep < pend ? p + pstep : nblocks);
-#endif
         {
-#ifdef LTC_EXP_NOLOAD
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] = make_float2((float)(t - n0), (float)(r + cnt));
-#else
             const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, ltc_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) sv[r] = prc_buf_load_c64(rs, vslot + 2048u * r, 0u);
-#endif
         }
         // one rotation on the way out: from this bin's frame to the frame of whoever reads the stream next
         const bool rot_out = a.rot || a.rot2;
@@ -117,9 +100,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
             if (ROT_IN) ibase = make_float2(p1.x, -p1.y);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifndef LTC_EXP_NOFFT       // timing ablation only (wrong results): no transforms, the memory pattern alone
         ft4096_inv<0>(y, f);
-#endif
         // last `peek` outputs of the block: rho samples whose ramp restarted carry gamma instead of 1
         if (a.rot && peek > 0 && n0 + cnt > n - peek) {
             const float2 g1 = a.gamma_m1;
@@ -157,18 +138,14 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
             const bool in = idx >= ext && idx < ext + cnt;
             y[r] = in ? o : make_float2(0.f, 0.f);
         }
-#ifndef LTC_EARLY_PREFETCH
         // the next block's spectrum flies under the forward transform: issued here and not before the inverse, its 32 landing
         // registers are free during the inverse, which is what lets the T2 twiddles stay in registers without spills
         // (measured: early prefetch + factored twiddles 1.53-1.55 ms, this 1.49 ms per 256 chunk-bins)
         __builtin_amdgcn_sched_barrier(0);
-        issue_x(p + pstep < pend ? p + pstep : nblocks);
+        issue_x(p + 1 < pend ? p + 1 : nblocks);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (a.has_next) {
-#ifndef LTC_EXP_NOFFT
             ft4096_fwd<1>(y, f);
-#endif
 #pragma unroll
             for (int m = 0; m < 16; ++m) ltc_cmac_bconj(wrs[m], y[m], xc[m]);
         }

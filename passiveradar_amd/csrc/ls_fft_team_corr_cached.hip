@@ -37,15 +37,11 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
 #pragma unroll
         for (int r = 0; r < 16; ++r) xn[r] = prc_buf_load_c64(rx, voff + 2048u * r, 0u);
     };
-#ifdef LTC_STRIDED
-    const int p0 = team, pstep = nteams, pend = npieces;
-#else
     const int per = (npieces + nteams - 1) / nteams;          // a contiguous run of pieces per team
-    const int p0 = team * per, pstep = 1, pend = p0 + per < npieces ? p0 + per : npieces;
-#endif
+    const int p0 = team * per, pend = p0 + per < npieces ? p0 + per : npieces;
     issue_x(p0 < pend ? p0 : npieces);
     ltc_loads_landed();
-    for (int p = p0; p < pend; p += pstep) {
+    for (int p = p0; p < pend; ++p) {
         const int n0 = p * B;
         const int cnt = (n - n0) < B ? (n - n0) : B;
         const int mstart = n0 - ext;
@@ -107,9 +103,9 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
             for (int m = 0; m < 8; ++m)
                 cp[FT_THREADS * m + t] = make_float4(x[2 * m].x, x[2 * m].y, x[2 * m + 1].x, x[2 * m + 1].y);
         }
-#ifndef LTC_EXP_NOUP                  // timing ablation, never shipped: without the reference piece's transform (an upper
-        ft4096_fwd<1>(up, f);         // bound for what pruning it -- FFT(piece) = X_p - FFT(history) -- could save)
-#endif
+        // the reference piece's own transform: 0.155 of the kernel's 1.65 ms, the upper bound for what pruning it --
+        // FFT(piece) = X_p - FFT(history) -- could save
+        ft4096_fwd<1>(up, f);
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
             float2 w = Wrr[FT_THREADS * m];
@@ -125,7 +121,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
                 u[r] = cmul(u[r], cmul(sbase, st));
             }
         }
-        issue_x(p + pstep < pend ? p + pstep : npieces);
+        issue_x(p + 1 < pend ? p + 1 : npieces);
         __builtin_amdgcn_sched_barrier(0);
         ft4096_fwd<0>(u, f);
         if (FT_NBUF == 2) ft_team_sync();                     // three transforms per piece: the next piece starts at buffer 0 again

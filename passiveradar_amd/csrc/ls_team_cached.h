@@ -38,9 +38,7 @@ static inline int ltc_piece(int T, int align) {
 // compiler's wait has to cover both, and it becomes an s_waitcnt vmcnt(0) on every iteration -- which also waits for the
 // stores of the previous piece (vmcnt counts loads and stores in order on gfx9).  tools/ubench/stream4.hip: +5 % of HBM rate.
 __device__ __forceinline__ void ltc_loads_landed() {
-#ifndef LTC_NO_WAIT_FIRST
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt and lgkmcnt untouched
-#endif
 }
 
 static inline void ltc_fill(LsFftArgs& a, double theta) {      // a.piece: set by the plan (fill_xa)

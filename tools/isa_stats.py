@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Instruction mix per basic block of a gfx950 assembly listing (hipcc -save-temps .s file).
+"""Instruction mix per basic block of a gfx950 assembly listing (make -C passiveradar_amd/csrc asm, or a hipcc -save-temps .s file).
 
     python tools/isa_stats.py file.s [kernel-name-substring]
 
