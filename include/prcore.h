@@ -27,6 +27,12 @@
  *     magic (a host built against a pre-600 header has the first field of the old layout there), a struct_size below
  *     the version-600 layout or not a multiple of 4 is PRC_EINVAL with a message naming the sizes -- a host built
  *     against another layout can never make the library read past its struct.
+ *   - memory: an entry point reads block / frame / stream b of an input only inside [b*stride, b*stride + extent) elements
+ *     -- and a CAF frame only below n_valid -- and writes only inside the documented extents of its outputs: what lies
+ *     before the first block, between two blocks or after the last one is neither used in a result nor changed.  Data
+ *     pointers need only the alignment of their element type (complex64: 8 bytes, int8 raw: any address).  No result
+ *     depends on what a plan, a caller's workspace or the library's scratch was used for before
+ *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
