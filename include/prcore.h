@@ -32,7 +32,8 @@
  *     before the first block, between two blocks or after the last one is neither used in a result nor changed.  Data
  *     pointers need only the alignment of their element type (complex64: 8 bytes, int8 raw: any address).  No result
  *     depends on what a plan, a caller's workspace or the library's scratch was used for before
- *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this).
+ *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
+ *     two display entry points).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -49,7 +50,8 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 630   /* 630: prc_strack_desc, prc_strack_record, prc_strack_workspace_bytes, prc_strack_run
+#define PRC_VERSION 640   /* 640: prc_display_limits, prc_display_rgba (the render loop's percentile limits and colour map on device);
+                             630: prc_strack_desc, prc_strack_record, prc_strack_workspace_bytes, prc_strack_run
                              (simple_target_tracker on device), prc_persistence (plotting_tools.persistence on device);
                              620: prc_gal_execute, prc_gal_workspace_bytes (GAL_JPE on device);
                              610: prc_track_desc, prc_track_record, prc_track_plan_create / _destroy, prc_track_measure, prc_track_run
@@ -536,6 +538,33 @@ int prc_strack_run(const prc_strack_desc* desc, const void* frames, int32_t nfra
 #define PRC_PERSISTENCE_TERMS_PER_LAUNCH 256
 int prc_persistence(const void* frames, int32_t in_dtype, int64_t frame_elems, int32_t nframes, int32_t k_first,
                     int32_t k_count, int32_t hold, double decay, void* out, int32_t out_dtype, void* stream);
+
+/* ---- display frames: range_doppler_plot.py:72-92 (np.percentile limits, imshow's Normalize + colour map) ------------- */
+/* Frames are [nframes][H][W] (H Doppler rows, W range columns) of `dtype` (prc_real_dtype); a float32 frame is taken as
+ * its values widened to float64 (not NumPy's float32 percentile arithmetic).  All arithmetic is float64, every operation
+ * rounded on its own, so limits and pixels are those of NumPy / matplotlib bit for bit.
+ * prc_display_limits: limits[f] = {percentile(frame f, p_lo), hi_scale * percentile(frame f, p_hi)}, NumPy's default
+ * (linear) percentile from the exact order statistics x(k), x(k+1) (radix select, one workgroup per frame) and NumPy's
+ * _lerp.  A frame holding a NaN has both limits NaN; as in NumPy, so has one whose interpolation meets Inf - Inf or
+ * Inf * 0 (a frame holding Inf).  -0.0 and +0.0 are one value and the sign of a zero limit is unspecified.
+ * prc_display_rgba: per cell v, xa = ((v - vmin) / (vmax - vmin)) * 256 with {vmin, vmax} = limits[f] read on the device
+ * (the two calls chain on a stream with no host round trip); the pixel is (0,0,0,0) for a NaN xa (matplotlib's "bad"
+ * colour), lut[0] for xa < 0, lut[255] for xa >= 256, else lut[trunc(xa)]; vmin == vmax gives lut[0] everywhere.
+ * Deviation: for vmin > vmax matplotlib raises; here the whole frame is (0,0,0,0) and the limits show why (a batched
+ * device call does not synchronise to raise).  lut_host: HOST 256 x RGBA8, or NULL for gnuplot2 (closed form at
+ * linspace(0, 1, 256), clipped, * 255 truncated, alpha 255); it travels in the kernel arguments.
+ * out: PRC_DISPLAY_PLOT writes s = fliplr(frame.T), out[f][r][c] = colour(frame[f][H-1-c][r]), shape [nframes][W][H][4];
+ * PRC_DISPLAY_STORED writes [nframes][H][W][4].
+ * Memory: reads only inside the nframes * frame_elems frame elements and the 2 * nframes limits, writes only the
+ * 2 * nframes limits / the 4 * nframes * H * W bytes of out; pointers need the alignment of their element (out: of one
+ * pixel, 4 bytes).  Neither allocates, copies nor synchronises.  PRC_EINVAL for a bad dtype or orient, a percentile
+ * outside [0, 100] or NaN, frame_elems < 1 or >= 2^31, H or W < 1 or H * W >= 2^31, nframes < 0 or a null pointer
+ * (lut_host excepted); nothing is written then.  nframes == 0 is a no-op. */
+typedef enum prc_display_orient { PRC_DISPLAY_PLOT = 0, PRC_DISPLAY_STORED = 1 } prc_display_orient;
+int prc_display_limits(const void* frames, int32_t dtype, int64_t frame_elems, int32_t nframes, double p_lo, double p_hi,
+                       double hi_scale, double* limits, void* stream);
+int prc_display_rgba(const void* frames, int32_t dtype, int32_t H, int32_t W, int32_t nframes, const double* limits,
+                     const uint8_t* lut_host, int32_t orient, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

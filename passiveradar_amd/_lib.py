@@ -114,9 +114,10 @@ STRACK_RECORD_DTYPE = np.dtype([("lock_mode", "<f8", (4,)), ("measurement", "<f8
                                 ("P", "<f8", (16,)), ("S", "<f8", (4,))])
 REAL_F32, REAL_F64 = 0, 1          # prc_real_dtype
 PERSISTENCE_TERMS_PER_LAUNCH = 256
+DISPLAY_PLOT, DISPLAY_STORED = 0, 1   # prc_display_orient
 
 
-MIN_LIB_VERSION = 630      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+MIN_LIB_VERSION = 640      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -196,6 +197,10 @@ _SIGNATURES = {
                                  C.c_void_p]),
     "prc_persistence": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_double, C.c_void_p, C.c_int32, C.c_void_p]),
+    "prc_display_limits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                     C.c_void_p, C.c_void_p]),
+    "prc_display_rgba": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_void_p, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),

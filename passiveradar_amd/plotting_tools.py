@@ -1,6 +1,10 @@
 """Drop-in for the reference's ``passiveRadar/plotting_tools.py``: ``persistence`` (the digital-phosphor sum that
 simple_kalman_tracker.py and range_doppler_plot.py apply to every frame they render), on the device, plus
-``persistence_stack``, every frame of that render loop in one launch.  Rendering itself (matplotlib) is not here."""
+``persistence_stack``, every frame of that render loop in one launch, and the rest of that loop's arithmetic:
+``display_limits`` (the two ``np.percentile`` calls per frame), ``render_frames`` (``imshow``'s Normalize and colour map,
+one RGBA8 pixel per cell, bit for bit what matplotlib computes) and ``render_maps`` (the whole chain from the complex
+maps).  Figure decoration (axes, labels, dpi, the tracker overlay, imshow's resampling onto figure pixels) is
+matplotlib's business and is not here."""
 from __future__ import annotations
 
 import numpy as np
@@ -8,7 +12,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 
-__all__ = ["persistence", "persistence_stack"]
+__all__ = ["persistence", "persistence_stack", "gnuplot2_lut", "display_limits", "render_frames", "render_maps"]
 
 
 def _weak_scalar(decay):
@@ -111,3 +115,205 @@ def persistence_stack(X, hold, decay, out_dtype=np.float64):
          _lib.REAL_F32 if odt == np.float32 else _lib.REAL_F64, None)
     out = np.moveaxis(do.download((L, H, W), odt), 0, 2)
     return out.astype(np.float32) if narrow else out
+
+
+# ---- display frames (range_doppler_plot.py:72-92) ----------------------------------------------------------------------
+_ORIENT = {"plot": _lib.DISPLAY_PLOT, "stored": _lib.DISPLAY_STORED}
+
+
+def gnuplot2_lut():
+    """matplotlib's 'gnuplot2' as it colours bytes: uint8 (256, 4), the closed form at np.linspace(0, 1, 256) clipped to
+    [0, 1], ``(lut * 255).astype(uint8)``, alpha 255 (the table prc_display_rgba builds for a NULL lut)"""
+    x = np.linspace(0, 1, 256)
+    r = x / 0.32 - 0.78125
+    g = 2 * x - 0.84
+    b = np.where(x < 0.25, 4 * x, np.where(x < 0.92, -2 * x + 1.84, x / 0.08 - 11.5))
+    lut = np.clip(np.stack([r, g, b, np.ones_like(x)], axis=1), 0, 1)
+    return (lut * 255).astype(np.uint8)
+
+
+def _check_percentiles(p_lo, p_hi, hi_scale):
+    p_lo, p_hi, hi_scale = float(p_lo), float(p_hi), float(hi_scale)
+    if not (0.0 <= p_lo <= 100.0 and 0.0 <= p_hi <= 100.0):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    return p_lo, p_hi, hi_scale
+
+
+def _check_lut(lut):
+    if lut is None:
+        return None
+    t = np.asarray(lut)
+    if t.dtype != np.uint8 or t.shape != (256, 4):
+        raise ValueError("lut is a uint8 (256, 4) RGBA table")
+    return np.ascontiguousarray(t)
+
+
+def _check_orient(orient):
+    if orient not in _ORIENT:
+        raise ValueError("orient is 'plot' (fliplr(data.T), as the reference shows it) or 'stored'")
+    return _ORIENT[orient]
+
+
+def _check_frame_shape(H, W):
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"frames of {H} x {W}: need H, W >= 1 and H * W < 2^31")
+
+
+def _device_stack(X, what):
+    """a device stack [L, H, W] as contiguous float32 (kept) or float64 (everything else), and its dtype code"""
+    import torch
+    if X.dim() != 3:
+        raise ValueError(f"{what} takes a device stack [L, H, W]")
+    x = (X if X.dtype == torch.float32 else X.to(torch.float64)).contiguous()
+    return x, (_lib.REAL_F32 if x.dtype == torch.float32 else _lib.REAL_F64)
+
+
+def _host_stack(X, what):
+    """a numpy (H, W, L) stack as contiguous [L, H, W], float32 (kept) or float64, and its dtype code"""
+    x = np.asarray(X)
+    if x.ndim != 3:
+        raise ValueError(f"{what} takes an (H, W, L) stack")
+    dt = np.float32 if x.dtype == np.float32 else np.float64
+    return np.ascontiguousarray(np.moveaxis(x, 2, 0), dtype=dt), (_lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64)
+
+
+def _limits(frames_ptr, code, elems, nframes, p_lo, p_hi, hi_scale, limits_ptr, stream):
+    check(lib().prc_display_limits(frames_ptr, code, int(elems), int(nframes), p_lo, p_hi, hi_scale, limits_ptr, stream))
+
+
+def _rgba(frames_ptr, code, H, W, nframes, limits_ptr, lut, orient, out_ptr, stream):
+    check(lib().prc_display_rgba(frames_ptr, code, int(H), int(W), int(nframes), limits_ptr,
+                                 None if lut is None else lut.ctypes.data, orient, out_ptr, stream))
+
+
+def display_limits(X, p_lo=35, p_hi=99, hi_scale=1.5):
+    """per frame ``(np.percentile(frame, p_lo), hi_scale * np.percentile(frame, p_hi))`` -- the vmin / vmax of
+    range_doppler_plot.py:75-76 -- from exact order statistics, bit for bit NumPy's float64 result (a float32 stack is
+    taken as its values widened to float64).  numpy (H, W, L) gives numpy (L, 2) float64; a torch device tensor
+    [L, H, W] gives a device (L, 2) float64 on the tensor's device and torch's current stream."""
+    p_lo, p_hi, hi_scale = _check_percentiles(p_lo, p_hi, hi_scale)
+    if _lib.is_device_tensor(X):
+        import torch
+        x, code = _device_stack(X, "display_limits")
+        L, H, W = x.shape
+        _check_frame_shape(H, W)
+        out = torch.empty((L, 2), dtype=torch.float64, device=x.device)
+        if L:
+            with torch.cuda.device(x.device):
+                _limits(x.data_ptr(), code, H * W, L, p_lo, p_hi, hi_scale, out.data_ptr(),
+                        _lib.torch_stream_ptr(x.device))
+        return out
+    f, code = _host_stack(X, "display_limits")
+    L, H, W = f.shape
+    _check_frame_shape(H, W)
+    if L == 0:
+        return np.empty((0, 2), np.float64)
+    _lib.require_gpu()
+    dx = _lib.DeviceBuffer(f.nbytes)
+    dx.upload(f)
+    dl = _lib.DeviceBuffer(L * 16)
+    _limits(dx.ptr, code, H * W, L, p_lo, p_hi, hi_scale, dl.ptr, None)
+    return dl.download((L, 2), np.float64)
+
+
+def render_frames(X, lut=None, limits=None, p_lo=35, p_hi=99, hi_scale=1.5, orient="plot"):
+    """``imshow(np.fliplr(frame.T), cmap=lut, vmin=limits[k, 0], vmax=limits[k, 1])`` per frame as RGBA8, one pixel per
+    cell: matplotlib's ``Normalize`` then ``Colormap.__call__(bytes=True)`` in float64, byte for byte.  ``lut``: a uint8
+    (256, 4) table, None = gnuplot2.  ``limits``: None = ``display_limits(X, p_lo, p_hi, hi_scale)``; else (L, 2) (host
+    array or device tensor), used as they are -- one fixed scale for a whole video.  A NaN cell (or NaN limits) gives
+    (0, 0, 0, 0), vmin == vmax gives lut[0]; where matplotlib raises for vmin > vmax, that frame is (0, 0, 0, 0)
+    throughout and the limits show why.  ``orient``: "plot" = fliplr(frame.T), result [L, W, H, 4]; "stored" = the
+    frames as they lie, [L, H, W, 4].  numpy (H, W, L) in gives numpy out; a torch device tensor [L, H, W] gives a
+    device tensor on the tensor's device and torch's current stream."""
+    p_lo, p_hi, hi_scale = _check_percentiles(p_lo, p_hi, hi_scale)
+    lut = _check_lut(lut)
+    oc = _check_orient(orient)
+    if _lib.is_device_tensor(X):
+        import torch
+        x, code = _device_stack(X, "render_frames")
+        L, H, W = x.shape
+        _check_frame_shape(H, W)
+        if limits is not None:
+            lim = limits if _lib.is_device_tensor(limits) else torch.from_numpy(np.asarray(limits, dtype=np.float64))
+            if tuple(lim.shape) != (L, 2):
+                raise ValueError(f"limits is (L, 2) = ({L}, 2)")
+            lim = lim.to(device=x.device, dtype=torch.float64).contiguous()
+        out = torch.empty((L, W, H, 4) if oc == _lib.DISPLAY_PLOT else (L, H, W, 4), dtype=torch.uint8, device=x.device)
+        if L:
+            with torch.cuda.device(x.device):
+                st = _lib.torch_stream_ptr(x.device)
+                if limits is None:
+                    lim = torch.empty((L, 2), dtype=torch.float64, device=x.device)
+                    _limits(x.data_ptr(), code, H * W, L, p_lo, p_hi, hi_scale, lim.data_ptr(), st)
+                _rgba(x.data_ptr(), code, H, W, L, lim.data_ptr(), lut, oc, out.data_ptr(), st)
+        return out
+    f, code = _host_stack(X, "render_frames")
+    L, H, W = f.shape
+    _check_frame_shape(H, W)
+    shape = (L, W, H, 4) if oc == _lib.DISPLAY_PLOT else (L, H, W, 4)
+    if limits is not None:
+        lim = np.ascontiguousarray(limits.cpu().numpy() if _lib.is_device_tensor(limits) else limits, dtype=np.float64)
+        if lim.shape != (L, 2):
+            raise ValueError(f"limits is (L, 2) = ({L}, 2)")
+    if L == 0:
+        return np.empty(shape, np.uint8)
+    _lib.require_gpu()
+    dx = _lib.DeviceBuffer(f.nbytes)
+    dx.upload(f)
+    dl = _lib.DeviceBuffer(L * 16)
+    if limits is None:
+        _limits(dx.ptr, code, H * W, L, p_lo, p_hi, hi_scale, dl.ptr, None)
+    else:
+        dl.upload(lim)
+    do = _lib.DeviceBuffer(L * H * W * 4)
+    _rgba(dx.ptr, code, H, W, L, dl.ptr, lut, oc, do.ptr, None)
+    return do.download(shape, np.uint8)
+
+
+RENDER_SLAB_BYTES = 1 << 28     # render_maps: float64 persistence frames alive at a time (default slab)
+
+
+def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, **render_kw):
+    """range_doppler_plot.py:43-92 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per frame
+    (CFAR_2D_abs; CFAR_2D for a real magnitude stack), persistence(CF, k, hold, decay) of the float64 CFAR maps for every
+    k, then ``render_frames(**render_kw)``.  ``xambg`` is a torch device tensor [L, H, W] (result: a device tensor
+    [L, W, H, 4], or [L, H, W, 4] for orient="stored") or numpy (H, W, L) as the script loads it (result: numpy; the
+    chain runs through torch).  The float64 persistence frames exist ``slab`` frames at a time (default: as many as fit
+    RENDER_SLAB_BYTES); a slab reads the ``hold - 1`` CFAR frames before its first one.  Given ``limits`` are (L, 2)."""
+    import torch
+    from .target_detection import CFAR_2D, CFAR_2D_abs
+    hold = int(hold)
+    if slab is not None and int(slab) < 1:
+        raise ValueError("slab is a number of frames >= 1")
+    if not _lib.is_device_tensor(xambg):
+        x = np.asarray(xambg)
+        if x.ndim != 3:
+            raise ValueError("render_maps takes (H, W, L) maps")
+        _lib.require_gpu()
+        x = np.ascontiguousarray(np.moveaxis(x, 2, 0), dtype=np.complex64 if np.iscomplexobj(x) else np.float32)
+        return render_maps(torch.from_numpy(x).cuda(), fw, gw, hold, decay, slab, **render_kw).cpu().numpy()
+    if xambg.dim() != 3:
+        raise ValueError("render_maps takes a device stack [L, H, W]")
+    L, H, W = xambg.shape
+    _check_frame_shape(H, W)
+    limits = render_kw.pop("limits", None)
+    if limits is not None:
+        limits = limits if _lib.is_device_tensor(limits) else torch.from_numpy(np.asarray(limits, dtype=np.float64))
+        if tuple(limits.shape) != (L, 2):
+            raise ValueError(f"limits is (L, 2) = ({L}, 2)")
+        limits = limits.to(device=xambg.device, dtype=torch.float64)
+    if L == 0:
+        return render_frames(torch.empty((0, H, W), dtype=torch.float64, device=xambg.device), limits=limits, **render_kw)
+    cf = CFAR_2D_abs(xambg, fw, gw) if xambg.is_complex() else CFAR_2D(xambg, fw, gw)
+    step = int(slab) if slab is not None else max(1, RENDER_SLAB_BYTES // (H * W * 8))
+    outs = []
+    for s0 in range(0, L, step):
+        s1 = min(L, s0 + step)
+        b0 = max(0, s0 - max(hold - 1, 0))                  # the first CFAR frame this slab's sums read
+        src = cf[b0:s1].to(torch.float64)                   # the reference's CF is float64: float64 products
+        st = torch.empty((s1 - s0, H, W), dtype=torch.float64, device=cf.device)
+        with torch.cuda.device(cf.device):
+            _run(src.data_ptr(), _lib.REAL_F64, H * W, s1 - b0, s0 - b0, s1 - s0, hold, decay, st.data_ptr(),
+                 _lib.REAL_F64, _lib.torch_stream_ptr(cf.device))
+        outs.append(render_frames(st, limits=None if limits is None else limits[s0:s1], **render_kw))
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
