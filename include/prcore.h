@@ -33,7 +33,7 @@
  *     pointers need only the alignment of their element type (complex64: 8 bytes, int8 raw: any address).  No result
  *     depends on what a plan, a caller's workspace or the library's scratch was used for before
  *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
- *     two display entry points).
+ *     two display entry points, tests/test_gpu_psd.py prc_welch).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -50,7 +50,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 640   /* 640: prc_display_limits, prc_display_rgba (the render loop's percentile limits and colour map on device);
+#define PRC_VERSION 650   /* 650: prc_welch_desc, prc_welch_rows, prc_welch_workspace_bytes, prc_welch (Welch spectra on device: the psd, csd and
+                             specgram of signal_preview.py);
+                             640: prc_display_limits, prc_display_rgba (the render loop's percentile limits and colour map on device);
                              630: prc_strack_desc, prc_strack_record, prc_strack_workspace_bytes, prc_strack_run
                              (simple_target_tracker on device), prc_persistence (plotting_tools.persistence on device);
                              620: prc_gal_execute, prc_gal_workspace_bytes (GAL_JPE on device);
@@ -565,6 +567,44 @@ int prc_display_limits(const void* frames, int32_t dtype, int64_t frame_elems, i
                        double hi_scale, double* limits, void* stream);
 int prc_display_rgba(const void* frames, int32_t dtype, int32_t H, int32_t W, int32_t nframes, const double* limits,
                      const uint8_t* lut_host, int32_t orient, uint8_t* out, void* stream);
+
+/* ---- Welch spectra: signal_preview.py:51-54, 68-71 (plt.psd = matplotlib.mlab.psd), mlab.csd, mlab.specgram ------------ */
+/* mlab._spectral_helper for complex input (sides='twosided', pad_to == NFFT): segment s of a channel is its samples
+ * [s * (nfft - noverlap), + nfft); per segment the mean is subtracted (detrend = 1), THEN the window applied, then the
+ * nfft-point DFT X_s taken.  With y == NULL out is float64 [nch][rows][nfft] of mean_s |X_s[k]|^2 * scale; with y given
+ * (same n, stride, step and in_dtype as x) it is complex128 [nch][rows][nfft] of mean_s conj(X_s[k]) Y_s[k] * scale.  The
+ * frequency axis is stored centred as mlab returns it (np.roll(., -nfft/2)): bin k sits at index (k + nfft/2) mod nfft.
+ * n < nfft is one segment, zero from n on (mlab pads it; the zeros take part in the mean); otherwise
+ * nseg = (n - nfft) / (nfft - noverlap) + 1 and the samples after the last whole segment are never read.
+ * Memory: channel c is read at element c * stride + i * step for i < n and nowhere else, an ELEMENT being one complex
+ * sample (one I,Q pair of the raw types: x + c * stride elements is 2 * c * stride scalars on); every element of out is
+ * written.  x, y need the alignment of their scalar type (int8: any address), out and workspace 8 bytes.
+ * Arithmetic: the samples are converted while they are loaded, the transform is float32 inside LDS with twiddles from
+ * float64 sincospi rounded once, |X|^2 or conj(X) Y is formed in float64 and summed in float64 in a fixed order (no
+ * atomics): two calls give the same bits, and prc_welch(x, x) has the auto spectrum as its real part, bit for bit, and a
+ * zero imaginary part.  Three kernels on `stream`; neither allocates nor synchronises.  `workspace`: DEVICE,
+ * prc_welch_workspace_bytes bytes, not shared by calls in flight (it holds the twiddles and the per-workgroup sums).
+ * PRC_EINVAL: nfft not a power of two in 64 .. 8192, noverlap outside [0, nfft), navg < 0, a detrend other than 0 / 1, a
+ * bad in_dtype, step < 1, n < 1, nch < 1, null pointers (y excepted), a bad descriptor header; PRC_ESHAPE: navg > nseg.
+ * prc_welch_rows and prc_welch_workspace_bytes are host arithmetic and need no device. */
+typedef struct prc_welch_desc {
+    uint32_t struct_size;  /* sizeof(prc_welch_desc) as the host compiled it (see Conventions)             */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int32_t nfft;          /* power of two, 64 .. 8192                                                */
+    int32_t noverlap;      /* 0 .. nfft-1; segment s starts at sample s*(nfft-noverlap)               */
+    int32_t navg;          /* 0: one output row = the mean of all segments; k > 0: row r = the mean of
+                              segments [r*k, (r+1)*k), rows = nseg / k (segments left over are dropped) */
+    int32_t detrend;       /* 0 none, 1 subtract the segment's mean before the window                 */
+    int32_t in_dtype;      /* prc_raw_dtype: I8/U8/I16/F32 interleaved I,Q scalars, or C64            */
+    int32_t step;          /* >= 1: sample i of a channel is element i*step (complex elements);
+                              2 = two channels interleaved sample by sample, signal_preview.py:33-34  */
+    double scale;          /* every output value is multiplied by this once, in float64               */
+} prc_welch_desc;
+#define PRC_WELCH_DESC_SIZE_650 40u
+int prc_welch_rows(const prc_welch_desc* desc, int64_t n, int64_t* nseg, int64_t* rows);
+int prc_welch_workspace_bytes(const prc_welch_desc* desc, int64_t n, int32_t nch, size_t* bytes);
+int prc_welch(const prc_welch_desc* desc, const void* x, const void* y /* NULL: auto spectrum */, int64_t n, int64_t stride,
+              int32_t nch, const float* window /* DEVICE float32[nfft] */, void* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ Submodules mirror the reference package layout:
     passiveradar_amd.clutter_removal.{LS_Filter, LS_Filter_Toeplitz, LS_Filter_Multiple, NLMS_filter}
     passiveradar_amd.signal_utils.{xcorr, frequency_shift}
     passiveradar_amd.config.getConfiguration
+    passiveradar_amd.spectral.{psd, csd, specgram, preview}   (matplotlib.mlab's Welch spectra; signal_preview.py)
 plus ``stream`` (the block pipeline of main.py:169-194, batched and sharded over GPUs) and
 ``scene`` (deterministic synthetic IQ).  All compute goes through libprcore.so (HIP, gfx950);
 there is no CPU fallback.

@@ -108,6 +108,12 @@ class StrackRecord(C.Structure):
                 ("estimate", C.c_double * 2), ("x", C.c_double * 4), ("P", C.c_double * 16), ("S", C.c_double * 4)]
 
 
+class WelchDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("nfft", C.c_int32), ("noverlap", C.c_int32), ("navg", C.c_int32), ("detrend", C.c_int32),
+                ("in_dtype", C.c_int32), ("step", C.c_int32), ("scale", C.c_double)]
+
+
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
 STRACK_RECORD_DTYPE = np.dtype([("lock_mode", "<f8", (4,)), ("measurement", "<f8", (2,)),
                                 ("measurement_idx", "<i8", (2,)), ("estimate", "<f8", (2,)), ("x", "<f8", (4,)),
@@ -117,7 +123,7 @@ PERSISTENCE_TERMS_PER_LAUNCH = 256
 DISPLAY_PLOT, DISPLAY_STORED = 0, 1   # prc_display_orient
 
 
-MIN_LIB_VERSION = 640      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+MIN_LIB_VERSION = 650      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -201,6 +207,10 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "prc_display_rgba": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p, C.c_void_p]),
+    "prc_welch_rows": (C.c_int, [C.POINTER(WelchDesc), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "prc_welch_workspace_bytes": (C.c_int, [C.POINTER(WelchDesc), C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_welch": (C.c_int, [C.POINTER(WelchDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),
