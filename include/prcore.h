@@ -33,7 +33,8 @@
  *     pointers need only the alignment of their element type (complex64: 8 bytes, int8 raw: any address).  No result
  *     depends on what a plan, a caller's workspace or the library's scratch was used for before
  *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
- *     two display entry points, tests/test_gpu_psd.py prc_welch).
+ *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
+ *     prc_normalize).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -50,7 +51,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 650   /* 650: prc_welch_desc, prc_welch_rows, prc_welch_workspace_bytes, prc_welch (Welch spectra on device: the psd, csd and
+#define PRC_VERSION 660   /* 660: prc_firdec_desc, prc_fir_decimate, prc_shift, prc_normalize_workspace_bytes, prc_normalize (the rest of
+                             signal_utils.py on device: decimate, channel_preprocessing, shift, offset_compensation, normalize);
+                             650: prc_welch_desc, prc_welch_rows, prc_welch_workspace_bytes, prc_welch (Welch spectra on device: the psd, csd and
                              specgram of signal_preview.py);
                              640: prc_display_limits, prc_display_rgba (the render loop's percentile limits and colour map on device);
                              630: prc_strack_desc, prc_strack_record, prc_strack_workspace_bytes, prc_strack_run
@@ -605,6 +608,51 @@ int prc_welch_rows(const prc_welch_desc* desc, int64_t n, int64_t* nseg, int64_t
 int prc_welch_workspace_bytes(const prc_welch_desc* desc, int64_t n, int32_t nch, size_t* bytes);
 int prc_welch(const prc_welch_desc* desc, const void* x, const void* y /* NULL: auto spectrum */, int64_t n, int64_t stride,
               int32_t nch, const float* window /* DEVICE float32[nfft] */, void* out, void* workspace, void* stream);
+
+/* ---- FIR decimator and the rest of signal_utils.py: decimate (:11-13), channel_preprocessing (:80-85), shift (:34-47),
+ *      normalize (:7-9) ------------------------------------------------------------------------------------------------- */
+/* prc_fir_decimate: y[j] = sum_{k < ntaps} taps[k] * xt[j*q + (ntaps-1)/2 - k], j < ceil(n / q), xt zero outside [0, n):
+ * scipy.signal.decimate(x, q, ntaps - 1, ftype='fir') -- zero phase, zero padding -- with the caller's taps.  xt[i] is
+ * sample i of the channel converted to complex64 (raw_dtype: interleaved I,Q scalars of deinterleave_IQ, or complex64) and,
+ * with mix != 0, multiplied by exp(j ph), ph = fl32(fl32(fl32(2 pi fc) fl32(i)) fl32(1 / fl32(fs))) + fl32(phase_offset):
+ * the float32 ramp of frequency_shift (:24-27), bit for bit what prc_frequency_shift computes.  deinterleave -> tune ->
+ * decimate is then ONE launch (channel_preprocessing) and the tuned samples never reach memory.
+ * Memory: channel c is read at element c*stride + i*step for i < n and nowhere else, an ELEMENT being one complex sample
+ * (one I,Q pair of the raw types); output j of channel c is written at complex64 element c*out_stride + j*out_step and
+ * nothing else is.  An (n, k) C-order array is step = k, stride = 1, nch = k (and out_step = k, out_stride = 1 for the
+ * (ceil(n/q), k) result); two channels interleaved sample by sample are step = 2, stride = 1.  x needs the alignment of its
+ * scalar type, out 8 bytes.  taps: DEVICE float32[ntaps].
+ * Two forms, chosen from q and ntaps alone: ntaps == 20 q + 1 and 2 <= q <= PRC_FIRDEC_TILE_MAX_Q stages a tile of tuned
+ * samples in LDS, phase-major, and every lane slides a register window along q short filters (taps wave-uniform); anything
+ * else runs one wavefront per output, lanes striding over the taps.  Sums are float32 in a fixed order, no atomics: two calls
+ * give the same bits.  One kernel on `stream`; neither allocates nor synchronises (it can be captured).  n == 0 is a no-op.
+ * PRC_EINVAL: a bad descriptor header, q < 1, ntaps < 1 or even, a bad raw_dtype, fs == 0 with mix, step < 1, n < 0,
+ * nch < 1 or > 65535, out_step < 1, null pointers; PRC_ESHAPE: ntaps >= 2^24. */
+typedef struct prc_firdec_desc {
+    uint32_t struct_size;  /* sizeof(prc_firdec_desc) as the host compiled it (see Conventions)            */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int32_t q;             /* keep every q-th filtered sample                                         */
+    int32_t ntaps;         /* odd; decimate's own filter is 20 q + 1 taps                             */
+    int32_t raw_dtype;     /* prc_raw_dtype of the input                                              */
+    int32_t mix;           /* 0: no rotation; 1: rotate sample i by the float32 ramp of fc, fs        */
+    double fc, fs;         /* frequency_shift(x, fc, fs, phase_offset)                                 */
+    double phase_offset;   /* scalar phase (radians), rounded to float32 as NumPy does                 */
+} prc_firdec_desc;
+#define PRC_FIRDEC_DESC_SIZE_660 48u
+#define PRC_FIRDEC_TILE_MAX_Q 59       /* the phase-major LDS tile is 2760 q bytes: 59 is the last q within 160 KiB */
+int prc_fir_decimate(const prc_firdec_desc* desc, const float* taps, const void* x, int64_t n, int64_t step, int64_t stride,
+                     int32_t nch, void* out, int64_t out_step, int64_t out_stride, void* stream);
+/* shift: y = x delayed by `shift` rows (shift < 0: advanced), zeros where nothing arrives; x, y: [rows][row_bytes] bytes,
+ * not overlapping.  Every byte of y is written, nothing else; x is read only where it is used.  Any alignment.
+ * PRC_EINVAL: null pointers, rows < 0, row_bytes < 1.  rows == 0 is a no-op. */
+int prc_shift(const void* x, void* y, int64_t rows, int64_t row_bytes, int64_t shift, void* stream);
+/* normalize: y = x / mean|x| over all n elements; is_complex = 0: float32, 1: complex64 (|x| = hypotf).  |x| is summed
+ * in float64, per workgroup into `workspace` (prc_normalize_workspace_bytes bytes, DEVICE, 8-byte aligned, not shared by
+ * calls in flight), the partial sums are added in workgroup order, the mean is rounded to float32 once and every element is
+ * divided by it in float32.  Two kernels on `stream`, no atomics, two calls give the same bits; neither allocates nor
+ * synchronises.  y may be x.  PRC_EINVAL: null pointers, n < 1, is_complex not 0 / 1. */
+int prc_normalize_workspace_bytes(int64_t n, size_t* bytes);
+int prc_normalize(const void* x, void* y, int64_t n, int32_t is_complex, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

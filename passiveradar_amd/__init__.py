@@ -4,7 +4,8 @@ Max-Manning/passiveRadar: fast_xambg + LS/NLMS clutter filters).
 Submodules mirror the reference package layout:
     passiveradar_amd.range_doppler_processing.fast_xambg
     passiveradar_amd.clutter_removal.{LS_Filter, LS_Filter_Toeplitz, LS_Filter_Multiple, NLMS_filter}
-    passiveradar_amd.signal_utils.{xcorr, frequency_shift}
+    passiveradar_amd.signal_utils.{xcorr, frequency_shift, deinterleave_IQ, resample, find_channel_offset, decimate,
+                                   channel_preprocessing, shift, offset_compensation, normalize}
     passiveradar_amd.config.getConfiguration
     passiveradar_amd.spectral.{psd, csd, specgram, preview}   (matplotlib.mlab's Welch spectra; signal_preview.py)
 plus ``stream`` (the block pipeline of main.py:169-194, batched and sharded over GPUs) and

@@ -114,6 +114,14 @@ class WelchDesc(_Desc):
                 ("in_dtype", C.c_int32), ("step", C.c_int32), ("scale", C.c_double)]
 
 
+class FirdecDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("q", C.c_int32), ("ntaps", C.c_int32), ("raw_dtype", C.c_int32), ("mix", C.c_int32),
+                ("fc", C.c_double), ("fs", C.c_double), ("phase_offset", C.c_double)]
+
+
+FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
+
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
 STRACK_RECORD_DTYPE = np.dtype([("lock_mode", "<f8", (4,)), ("measurement", "<f8", (2,)),
                                 ("measurement_idx", "<i8", (2,)), ("estimate", "<f8", (2,)), ("x", "<f8", (4,)),
@@ -123,7 +131,7 @@ PERSISTENCE_TERMS_PER_LAUNCH = 256
 DISPLAY_PLOT, DISPLAY_STORED = 0, 1   # prc_display_orient
 
 
-MIN_LIB_VERSION = 650      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+MIN_LIB_VERSION = 660      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -211,6 +219,11 @@ _SIGNATURES = {
     "prc_welch_workspace_bytes": (C.c_int, [C.POINTER(WelchDesc), C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "prc_welch": (C.c_int, [C.POINTER(WelchDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "prc_fir_decimate": (C.c_int, [C.POINTER(FirdecDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                   C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "prc_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "prc_normalize_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "prc_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),

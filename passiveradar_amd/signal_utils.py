@@ -1,5 +1,10 @@
-"""Drop-ins for the two ``passiveRadar/signal_utils.py`` helpers that sit on the hot path."""
+"""Drop-ins for ``passiveRadar/signal_utils.py``: every function of the module, on the device."""
 from __future__ import annotations
+
+import collections
+import ctypes as C
+import operator
+import threading
 
 import numpy as np
 
@@ -7,7 +12,7 @@ from . import _lib, engine
 from ._lib import check, lib
 
 __all__ = ["xcorr", "frequency_shift", "deinterleave_IQ", "resample", "front_end", "find_channel_offset",
-           "decimate_iir"]
+           "decimate_iir", "decimate", "channel_preprocessing", "shift", "offset_compensation", "normalize"]
 
 
 def _xcorr_equal_lengths(s1, s2, nlead, nlag):
@@ -195,3 +200,256 @@ def front_end(raw, input_chunk_length, offset_freq, input_sample_rate, up, dn, m
         plan.execute(dr.ptr + b0 * icl * isz, do.ptr + 8 * b0 * plan.n_out, nb, icl, plan.n_out,
                      offset_freq, input_sample_rate, phases[b0:b0 + nb], True)
     return do.download((nblocks * plan.n_out,), np.complex64)
+
+
+# ---- decimate, channel_preprocessing, shift, offset_compensation, normalize (signal_utils.py:7-13, 34-71, 80-85) -------
+_RAW_NUMPY = ("int8", "uint8", "int16", "float32")
+_TAP_CACHE_ENTRIES = 16
+_taps = collections.OrderedDict()        # (device, q) -> DeviceBuffer of the float32 taps
+_taps_lock = threading.Lock()
+_MAX_CHANNELS = 65535                    # channels per prc_fir_decimate launch
+
+
+def _decimate_taps(q):
+    """scipy.signal.decimate's FIR for ftype='fir', n = 20 q: firwin(20 q + 1, 1 / q, window='hamming'), as float32.
+    q == 1 raises firwin's ValueError (a cut-off at Nyquist), as in the reference."""
+    from scipy.signal import firwin
+    if q < 1:
+        raise ValueError("q must be a positive integer")
+    return firwin(20 * q + 1, 1.0 / q, window="hamming").astype(np.float32)
+
+
+def _device_taps(q, device):
+    """decimate's float32 taps on the device, from a small cache keyed by q"""
+    key = (device, q)
+    with _taps_lock:
+        buf = _taps.get(key)
+        if buf is None:
+            h = _decimate_taps(q)
+            buf = _lib.DeviceBuffer(h.nbytes)
+            buf.upload(h)
+            _taps[key] = buf
+            while len(_taps) > _TAP_CACHE_ENTRIES:
+                _taps.popitem(last=False)
+        else:
+            _taps.move_to_end(key)
+        return buf
+
+
+def _result_dtype(dtype):
+    """what NumPy / SciPy return for an input of this dtype: complex64, complex128, float32 and float64 stay, the rest
+    (integers, bool, float16) is float64"""
+    dtype = np.dtype(dtype)
+    if dtype in (np.complex64, np.complex128, np.float32, np.float64):
+        return dtype
+    if dtype.kind == "c":
+        return np.dtype(np.complex128)
+    return np.dtype(np.float64)
+
+
+def _fir_decimate(q, code, mix, fc, Fs, x_ptr, x_scalar_bytes, n, k, out_ptr, taps_ptr, stream):
+    """prc_fir_decimate on an (n, k) C-order input and a (ceil(n / q), k) complex64 output, 65535 channels per launch"""
+    d = _lib.FirdecDesc()
+    d.q, d.ntaps, d.raw_dtype, d.mix = q, 20 * q + 1, code, int(mix)
+    d.fc, d.fs, d.phase_offset = float(fc), float(Fs), 0.0
+    for c0 in range(0, k, _MAX_CHANNELS):
+        nch = min(_MAX_CHANNELS, k - c0)
+        check(lib().prc_fir_decimate(C.byref(d), taps_ptr, x_ptr + c0 * x_scalar_bytes, n, k, 1, nch, out_ptr + 8 * c0, k, 1,
+                                     stream))
+
+
+def _torch_raw_code(x, what):
+    import torch
+    names = {torch.int8: "int8", torch.uint8: "uint8", torch.int16: "int16", torch.float32: "float32"}
+    if x.dtype not in names:
+        raise ValueError(f"{what}: a device tensor holds int8, uint8, int16 or float32 interleaved I,Q scalars")
+    return _lib.RAW_DTYPES[names[x.dtype]]
+
+
+def decimate(x, q):
+    """signal_utils.py:11-13: ``scipy.signal.decimate(x, q, 20*q, ftype='fir', axis=0)`` -- the zero-phase Hamming FIR of
+    20 q + 1 taps with zero padding, every q-th sample, along axis 0 (every trailing index is a channel of its own).
+    The device computes in complex64 with float32 taps; the result comes back in the reference's dtype (complex64,
+    complex128, float32 and float64 stay, integers give float64), so a complex128 or float64 result carries float32
+    accuracy.  A complex64 torch device tensor is read in place on torch's current stream and gives a device tensor."""
+    q = operator.index(q)                                   # TypeError for a float, as scipy.signal.decimate
+    h_check = _decimate_taps(q)                             # ValueError for q == 1, before any device call
+    del h_check
+    if _lib.is_device_tensor(x):
+        import torch
+        if x.dtype != torch.complex64:
+            raise ValueError("decimate: a device tensor is complex64")
+        if x.dim() < 1:
+            raise ValueError("decimate: x has no axis 0")
+        n, trail = int(x.shape[0]), tuple(x.shape[1:])
+        k = int(np.prod(trail, dtype=np.int64))
+        out = torch.empty((-(-n // q),) + trail, dtype=torch.complex64, device=x.device)
+        if n == 0 or k == 0:
+            return out
+        with torch.cuda.device(x.device):
+            xc = x.contiguous()
+            taps = _device_taps(q, x.device.index)
+            _fir_decimate(q, _lib.RAW_DTYPES["complex64"], 0, 0.0, 1.0, xc.data_ptr(), 8, n, k, out.data_ptr(), taps.ptr,
+                          _lib.torch_stream_ptr(x.device))
+        return out
+    xin = np.asarray(x)
+    if xin.ndim < 1:
+        raise ValueError("decimate: x has no axis 0")
+    odt = _result_dtype(xin.dtype)
+    n, trail = xin.shape[0], xin.shape[1:]
+    k = int(np.prod(trail, dtype=np.int64))
+    n_out = -(-n // q)
+    if n == 0 or k == 0:
+        return np.zeros((n_out,) + trail, odt)
+    xc = np.ascontiguousarray(xin, dtype=np.complex64)
+    _lib.require_gpu()
+    taps = _device_taps(q, _lib.current_device())
+    st = engine.staging()
+    dx = st.get("fd_x", xc.nbytes)
+    do = st.get("fd_o", 8 * n_out * k)
+    dx.upload(xc)
+    _fir_decimate(q, _lib.RAW_DTYPES["complex64"], 0, 0.0, 1.0, dx.ptr, 8, n, k, do.ptr, taps.ptr, None)
+    y = do.download((n_out,) + trail, np.complex64)
+    return y.astype(odt) if odt.kind == "c" else y.real.astype(odt)
+
+
+def channel_preprocessing(sig, dec, fc, Fs):
+    """signal_utils.py:80-85: ``decimate(frequency_shift(deinterleave_IQ(sig), fc, Fs), dec)``, complex64 of length
+    ceil((len(sig) // 2) / dec), in ONE launch: the raw int8 / uint8 / int16 / float32 scalars are converted and rotated
+    (the reference's float32 phase ramp) while a tile is staged, and the tuned stream never reaches memory.  Other dtypes are
+    taken as float32.  A raw torch device tensor is read in place on torch's current stream and gives a device tensor."""
+    dec = operator.index(dec)
+    h_check = _decimate_taps(dec)
+    del h_check
+    if float(Fs) == 0.0:
+        raise ZeroDivisionError("channel_preprocessing: Fs is zero")
+    if _lib.is_device_tensor(sig):
+        import torch
+        code = _torch_raw_code(sig, "channel_preprocessing")
+        if sig.dim() != 1:
+            raise ValueError("channel_preprocessing takes a one-dimensional array of interleaved I,Q scalars")
+        n = int(sig.shape[0]) // 2
+        out = torch.empty((-(-n // dec),), dtype=torch.complex64, device=sig.device)
+        if n == 0:
+            return out
+        with torch.cuda.device(sig.device):
+            raw = sig.contiguous()
+            taps = _device_taps(dec, sig.device.index)
+            _fir_decimate(dec, code, 1, fc, Fs, raw.data_ptr(), raw.element_size(), n, 1, out.data_ptr(), taps.ptr,
+                          _lib.torch_stream_ptr(sig.device))
+        return out
+    raw = np.ascontiguousarray(sig)
+    if raw.ndim != 1:
+        raise ValueError("channel_preprocessing takes a one-dimensional array of interleaved I,Q scalars")
+    if str(raw.dtype) not in _RAW_NUMPY:
+        raw = raw.astype(np.float32)
+    n = raw.shape[0] // 2
+    n_out = -(-n // dec)
+    if n == 0:
+        return np.zeros((0,), np.complex64)
+    _lib.require_gpu()
+    taps = _device_taps(dec, _lib.current_device())
+    st = engine.staging()
+    dr = st.get("cp_raw", raw.nbytes)
+    do = st.get("cp_out", 8 * n_out)
+    dr.upload(raw)
+    _fir_decimate(dec, _lib.RAW_DTYPES[str(raw.dtype)], 1, fc, Fs, dr.ptr, raw.dtype.itemsize, n, 1, do.ptr, taps.ptr, None)
+    return do.download((n_out,), np.complex64)
+
+
+def shift(x, n):
+    """signal_utils.py:34-47: x delayed by n samples along axis 0 (n < 0: advanced), zeros where nothing arrives; dtype
+    and shape are kept, ``n == 0`` returns x itself.  A torch device tensor gives a device tensor."""
+    if n == 0:
+        return x
+    n = operator.index(n)
+    if _lib.is_device_tensor(x):
+        import torch
+        if x.dim() < 1:
+            raise ValueError("shift: x has no axis 0")
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        rows = int(x.shape[0])
+        row_bytes = (x.numel() // rows) * x.element_size() if rows else 0
+        if rows == 0 or row_bytes == 0:
+            return out
+        with torch.cuda.device(x.device):
+            xc = x.contiguous()
+            check(lib().prc_shift(xc.data_ptr(), out.data_ptr(), rows, row_bytes, n, _lib.torch_stream_ptr(x.device)))
+        return out
+    xin = np.ascontiguousarray(x)
+    if xin.ndim < 1:
+        raise ValueError("shift: x has no axis 0")
+    if xin.dtype.hasobject:
+        raise ValueError("shift: object arrays have no device form")
+    rows = xin.shape[0]
+    row_bytes = (xin.size // rows) * xin.dtype.itemsize if rows else 0
+    if rows == 0 or row_bytes == 0:
+        return np.zeros_like(xin)
+    _lib.require_gpu()
+    st = engine.staging()
+    dx = st.get("sh_x", xin.nbytes)
+    dy = st.get("sh_y", xin.nbytes)
+    dx.upload(xin)
+    check(lib().prc_shift(dx.ptr, dy.ptr, rows, row_bytes, n, None))
+    return dy.download(xin.shape, xin.dtype)
+
+
+def offset_compensation(x1, x2, ns, ndec, nlag=2000):
+    """signal_utils.py:49-71: the offset of x2 against x1 from find_channel_offset on their first ``int(ns)`` samples,
+    then x2 shifted so that it lines up with x1 (zeros at the edge); x2 itself when the offset is 0.  Device tensors stay
+    on their device; finding the offset synchronises, as find_channel_offset does."""
+    ns = int(ns)
+    if _lib.is_device_tensor(x1) and _lib.is_device_tensor(x2):
+        import torch
+        with torch.cuda.device(x2.device):
+            s1 = x1[0:ns].to(device=x2.device, dtype=torch.complex64).contiguous()
+            s2 = x2[0:ns].to(torch.complex64).contiguous()
+            if s1.dim() != 1 or s2.dim() != 1:
+                raise ValueError("find_channel_offset takes one-dimensional signals")
+            dec = engine.cached_plan(("iirdec", int(ndec)), lambda: engine.IirDecimator(ndec))
+            am, _ = dec.channel_offset(s1, s1.shape[0], s2, s2.shape[0], int(nlag), None,
+                                       stream=_lib.torch_stream_ptr(x2.device))
+        os_ = (am - int(nlag)) * int(ndec)
+    else:
+        os_ = find_channel_offset(x1[0:ns], x2[0:ns], ndec, nlag)
+    if os_ == 0:
+        return x2
+    return shift(x2, os_)
+
+
+def normalize(x):
+    """signal_utils.py:7-9: ``x / mean(|x|)`` over all elements, any shape.  |x| is summed in float64 on the device and the
+    division is float32 (complex64); the result comes back in the reference's dtype (complex64, complex128, float32 and
+    float64 stay, integers give float64).  A float32 or complex64 torch device tensor gives a device tensor."""
+    if _lib.is_device_tensor(x):
+        import torch
+        if x.dtype not in (torch.float32, torch.complex64):
+            raise ValueError("normalize: a device tensor is float32 or complex64")
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        n = x.numel()
+        if n == 0:
+            return out
+        with torch.cuda.device(x.device):
+            xc = x.contiguous()
+            ws = C.c_size_t(0)
+            check(lib().prc_normalize_workspace_bytes(n, C.byref(ws)))
+            work = torch.empty((int(ws.value) // 8,), dtype=torch.float64, device=x.device)
+            check(lib().prc_normalize(xc.data_ptr(), out.data_ptr(), n, int(x.dtype == torch.complex64), work.data_ptr(),
+                                      _lib.torch_stream_ptr(x.device)))
+        return out
+    xin = np.asarray(x)
+    odt = _result_dtype(xin.dtype)
+    n = xin.size
+    if n == 0:
+        return np.zeros(xin.shape, odt)
+    cplx = odt.kind == "c"
+    xc = np.ascontiguousarray(xin, dtype=np.complex64 if cplx else np.float32)
+    _lib.require_gpu()
+    ws = C.c_size_t(0)
+    check(lib().prc_normalize_workspace_bytes(n, C.byref(ws)))
+    st = engine.staging()
+    dx = st.get("nz_x", xc.nbytes)
+    dw = st.get("nz_w", int(ws.value))
+    dx.upload(xc)
+    check(lib().prc_normalize(dx.ptr, dx.ptr, n, int(cplx), dw.ptr, None))
+    return dx.download(xin.shape, xc.dtype).astype(odt)
