@@ -65,6 +65,23 @@ PK_CMUL_FORMS(_s, "s")
 #undef PK_CMUL_FORMS
 __device__ __forceinline__ v2f pk_cmul(v2f a, v2f t) { return pk_cmul_q<false>(a, t, pk_cmul_p(a, t)); }
 __device__ __forceinline__ v2f pk_cmul_conj(v2f a, v2f t) { return pk_cmul_q<true>(a, t, pk_cmul_p(a, t)); }
+// a * b with the roundings of cmul (common.h) as -ffp-contract=on compiles it -- the a.y products rounded, the a.x products
+// fused onto them: p = (a.y b.y, a.y b.x), then (a.x b.x - p.x, a.x b.y + p.y).  Not those of mul_tw, which rounds a.x t.x.
+#define PK_CMULC_FORMS(sfx, T)                                                                                        \
+    __device__ __forceinline__ v2f pk_cmulc_p##sfx(v2f a, v2f b) {                                                    \
+        v2f p;                                                                                                        \
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(p) : "v"(a), T(b));                         \
+        return p;                                                                                                     \
+    }                                                                                                                 \
+    __device__ __forceinline__ v2f pk_cmulc_q##sfx(v2f a, v2f b, v2f p) {                                             \
+        v2f d;                                                                                                        \
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_lo:[0,0,1]" : "=v"(d) : "v"(a), T(b), "v"(p)); \
+        return d;                                                                                                     \
+    }                                                                                                                 \
+    __device__ __forceinline__ v2f pk_cmulc##sfx(v2f a, v2f b) { return pk_cmulc_q##sfx(a, b, pk_cmulc_p##sfx(a, b)); }
+PK_CMULC_FORMS(, "v")
+PK_CMULC_FORMS(_s, "s")
+#undef PK_CMULC_FORMS
 template <int DIR>
 __device__ __forceinline__ v2f pk_mul_tw(v2f a, v2f t) { return DIR > 0 ? pk_cmul(a, t) : pk_cmul_conj(a, t); }
 

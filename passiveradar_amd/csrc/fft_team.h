@@ -14,7 +14,7 @@
 //             T1 twiddle W_256^(n2 k1)                 LDS table [k1][n2], broadcast reads
 //             X1 exchange across the four waves        write (t, k1) | __syncthreads | read (16 m + lo, hi)
 //             S2 DFT16 over n2                         thread (k1, n3) = (hi, lo)
-//             T2 twiddle W_4096^(n3 (k1 + 16 k2))      16 per-thread constants
+//             T2 twiddle W_4096^(n3 (k1 + 16 k2))      16 per-thread constants (registers; FT_TW2_REGS < 16: the last ones in LDS)
 //             X2 exchange inside each 16-lane row      write (t, k2) | read (16 hi + j, lo); no workgroup barrier
 //             S3 DFT16 over n3                         thread (k1, k2) = (hi, lo), register k3
 //   inverse : the same stages backwards with conjugated twiddles, unnormalised (x 4096).
@@ -43,7 +43,20 @@
 #ifndef FT_NBUF
 #define FT_NBUF 2                       // exchange buffers: 2 = one barrier per forward transform; 1 = two barriers, half the LDS
 #endif
-#define FT_LDS_ELEMS (FT_TW1 + FT_NBUF * FT_BUF)   // float2 elements of LDS per workgroup (71 680 B with two buffers)
+// T2 twiddles a thread keeps in registers; those of registers k2 >= FT_TW2_REGS are read from LDS where they are used (two
+// ds_read_b64 per transform for each one parked).  For kernels that need the last few VGPRs: 16 - FT_TW2_REGS pairs come free.
+#ifndef FT_TW2_REGS
+#define FT_TW2_REGS 16
+#endif
+#if FT_TW2_REGS < 1 || FT_TW2_REGS > 16
+#error "FT_TW2_REGS: 1..16 of the 16 T2 twiddles stay in registers"
+#endif
+#if defined(FT_TW2_FACTORED) && FT_TW2_REGS != 16
+#error "FT_TW2_REGS applies to the table form of the T2 twiddles, not to FT_TW2_FACTORED"
+#endif
+#define FT_TW2_LDS ((16 - FT_TW2_REGS) * FT_THREADS)   // parked T2 twiddles, behind the exchange buffers: [k2 - FT_TW2_REGS][t]
+// float2 elements of LDS per workgroup (71 680 B with two buffers and every T2 twiddle in registers)
+#define FT_LDS_ELEMS (FT_TW1 + FT_NBUF * FT_BUF + FT_TW2_LDS)
 #define FT_GTAB (FT_TW1 + FT_P)         // global table: TW1 then W_4096^m, m = 0..4095
 
 struct FtLane {
@@ -56,7 +69,10 @@ struct FtLane {
     float2 tw2b;        // W_4096^(lo hi); the k2 part W_256^(lo k2) comes from the TW1 table (tw2t[16 k2])
     const float2* tw2t; // lds + lo
 #else
-    float2 tw2[16];     // W_4096^(lo (hi + 16 k2))
+    float2 tw2[FT_TW2_REGS];   // W_4096^(lo (hi + 16 k2)), k2 < FT_TW2_REGS
+#if FT_TW2_REGS < 16
+    const float2* tw2l; // lds + FT_TW1 + FT_NBUF FT_BUF + t : the same for k2 >= FT_TW2_REGS at tw2l[256 (k2 - FT_TW2_REGS)]
+#endif
 #endif
 };
 
@@ -64,13 +80,16 @@ struct FtLane {
 __device__ __forceinline__ float2 ft_tw2(const FtLane& f, int k2) {
 #if defined(FT_TW2_FACTORED)
     return k2 == 0 ? f.tw2b : cmul(f.tw2b, f.tw2t[16 * k2]);
+#elif FT_TW2_REGS < 16
+    // thread major: consecutive lanes read consecutive float2 (one ds_read_b64 without bank conflicts)
+    return k2 < FT_TW2_REGS ? f.tw2[k2] : f.tw2l[FT_THREADS * (k2 - FT_TW2_REGS)];
 #else
     return f.tw2[k2];
 #endif
 }
 
-// Fill the TW1 table in LDS and this thread's T2 constants from the host-made global table; ends with
-// __syncthreads().  lds: FT_LDS_ELEMS float2.
+// Fill the TW1 table in LDS and this thread's T2 constants (registers, and LDS for k2 >= FT_TW2_REGS) from the host-made
+// global table; ends with __syncthreads().  lds: FT_LDS_ELEMS float2.
 __device__ __forceinline__ FtLane ft_setup(float2* lds, const float2* __restrict__ gtab) {
     FtLane f;
     f.t = threadIdx.x;
@@ -86,7 +105,14 @@ __device__ __forceinline__ FtLane ft_setup(float2* lds, const float2* __restrict
     f.tw2t = lds + lo;
 #else
 #pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) f.tw2[k2] = gtab[FT_TW1 + ((lo * (hi + 16 * k2)) & (FT_P - 1))];
+    for (int k2 = 0; k2 < FT_TW2_REGS; ++k2) f.tw2[k2] = gtab[FT_TW1 + ((lo * (hi + 16 * k2)) & (FT_P - 1))];
+#if FT_TW2_REGS < 16
+    float2* park = x + FT_NBUF * FT_BUF + f.t;          // written and read by this thread only
+#pragma unroll
+    for (int k2 = FT_TW2_REGS; k2 < 16; ++k2)
+        park[FT_THREADS * (k2 - FT_TW2_REGS)] = gtab[FT_TW1 + ((lo * (hi + 16 * k2)) & (FT_P - 1))];
+    f.tw2l = park;
+#endif
 #endif
     __syncthreads();
     return f;

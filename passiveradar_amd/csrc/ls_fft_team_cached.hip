@@ -9,13 +9,23 @@
 // One workgroup (four wavefronts, fft_team.h) per piece.  Slot idx = 256 r + t of a piece at n0 holds rho[n0 - ext + idx]
 // for the block spectrum X_p and the (surveillance / cleaned) sample n0 + idx - ext in slots [ext, ext + cnt) for the
 // correlation inputs, where the slot origin ext = T - 1 rounded up to 16 samples (ltc_piece: pieces then start on
-// 128-byte lines; the extra history slots are harmless to the overlap-save FIR and to the lags 0 .. T-1).  Compiled with one exchange buffer (FT_NBUF = 1, Makefile): 36 KB of exchange + 32 KB of
-// per-thread spectrum (autocorrelation accumulator / tap spectrum) = 68 KB per workgroup, two workgroups per CU.
+// 128-byte lines; the extra history slots are harmless to the overlap-save FIR and to the lags 0 .. T-1).  Compiled with one
+// exchange buffer (FT_NBUF = 1, Makefile): 36 KB of exchange + 4 KB of parked T2 twiddles (this file only) + 32 KB of
+// per-thread spectrum (autocorrelation accumulator / tap spectrum) = 72 KB per workgroup here, 68 KB in the first-bin kernel;
+// two workgroups per CU either way (160 KB).
 // This file: the fused FIR + correlation kernel; the first-bin kernel sits in ls_fft_team_corr_cached.hip (its own unit so
-// that the two can be built with different FT_* options: A/B runs with tools/build_variant.sh + tools/ab_ls_team.sh).  Both
-// keep the T2 twiddles in registers: the first-bin kernel is VALU-bound (13 % slower with the factored form), and the fused
-// kernel has the registers since the next block's prefetch moved behind the inverse transform (with the prefetch in front of
-// it the twiddles spilled: 2.02 ms; factored twiddles 1.53-1.55 ms; this arrangement 1.49 ms per 256 chunk-bins).
+// that the two can be built with different FT_* options: A/B runs with tools/build_variant.sh).  Both run the transforms and
+// their pointwise work on packed-f32 instructions (FT_PK) with the T2 twiddles as table values, not factored: the first-bin
+// kernel is VALU-bound (13 % slower with the factored form) and keeps all 16 in registers.  The fused kernel is limited by
+// instruction issue and by HBM at once and sits at the register limit of two waves per SIMD: the packed transforms need one
+// VGPR more than the scalar ones, so it keeps 14 twiddles in registers and reads the last two from a thread-major LDS area
+// where they are used (FT_TW2_REGS = 14: two ds_read_b64 per transform; 254 / 256 VGPRs for <false> / <true>, no spill, no
+// scratch).  Same table values, same roundings in the same order as the scalar build.  The registers for the others are there
+// since the next block's prefetch moved behind the inverse transform (with the prefetch in front of it the twiddles spilled:
+// 2.02 ms; factored twiddles 1.53-1.55 ms; that arrangement on scalar transforms 1.49 ms per 256 chunk-bins).
+// Pointwise work on packed forms (ltc_cmul, ltc_sub, ltc_cmac_bconj: each rounds as its scalar form under -ffp-contract=on):
+// X.H, the subtraction, the output rotation, the correlation update.  Left scalar: the input rotation of <true> (one launch
+// per chain), the peek correction and the scaling of the tap spectrum (once per team).
 #include "ls_team_cached.h"
 
 // FIR of bin i fused with the cross-correlation of bin i+1: per piece the team reads X_p (cache, 32 KB) and the
@@ -81,7 +91,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
 #pragma unroll
         for (int r = 0; r < 16; ++r) xc[r] = xn[r];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) y[r] = cmul(xc[r], Hs[FT_THREADS * r]);
+        for (int r = 0; r < 16; ++r) y[r] = ltc_cmul(xc[r], Hs[FT_THREADS * r]);
         __builtin_amdgcn_sched_barrier(0);
         {
             const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, ltc_clampu(cnt) * 8u);
@@ -129,8 +139,8 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
                 st.y = -st.y;
                 sin_ = cmul(sin_, cmul(ibase, st));
             }
-            float2 o = make_float2(sin_.x - y[r].x, sin_.y - y[r].y);
-            if (rot_out) o = cmul(o, cmul(obase, a.step[r]));
+            float2 o = ltc_sub(sin_, y[r]);
+            if (rot_out) o = ltc_cmul(o, ltc_cmul_u(obase, a.step[r]));
             prc_buf_store_c64(ro, vslot + 2048u * r, 0u, o);
             // the stored piece (already in the next bin's frame) stays in registers as that bin's correlation
             // input: slots [ext, ext+cnt) only (the other slots of y are circular-convolution garbage)

@@ -23,6 +23,30 @@ __device__ __forceinline__ void ltc_cmac_bconj(float2& w, float2 u, float2 x) { 
 #endif
 }
 
+// The fused kernel's pointwise products and differences: cmul / a - b of common.h, on packed instructions under FT_PK (same
+// roundings: fft_pk.h).  ltc_cmul_u: b is uniform (a kernel argument) and is read from its SGPR pair.
+__device__ __forceinline__ float2 ltc_cmul(float2 a, float2 b) {
+#ifdef FT_PK
+    return pk_to(pk_cmulc(pk_from(a), pk_from(b)));
+#else
+    return cmul(a, b);
+#endif
+}
+__device__ __forceinline__ float2 ltc_cmul_u(float2 a, float2 b) {
+#ifdef FT_PK
+    return pk_to(pk_cmulc_s(pk_from(a), pk_from(b)));
+#else
+    return cmul(a, b);
+#endif
+}
+__device__ __forceinline__ float2 ltc_sub(float2 a, float2 b) {
+#ifdef FT_PK
+    return pk_to(pk_sub(pk_from(a), pk_from(b)));
+#else
+    return make_float2(a.x - b.x, a.y - b.y);
+#endif
+}
+
 // Samples per piece.  The slot origin E (history in slots [0, E), the piece in [E, E + B)) is T - 1 rounded up to 16
 // samples, so that every piece starts on a 128-byte line of the streams (tools/ubench/stream4.hip: +4 .. 8 % of HBM rate
 // for the same bytes); align = 0 keeps E = T - 1 (A/B runs).  The plan decides ONCE (PRC_OPT_LS_TEAM_ALIGN at
