@@ -51,7 +51,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 660   /* 660: prc_firdec_desc, prc_fir_decimate, prc_shift, prc_normalize_workspace_bytes, prc_normalize (the rest of
+#define PRC_VERSION 670   /* 670: prc_ls_svd_workspace_bytes, prc_ls_svd_execute, prc_ls_svd_set_profiling, prc_ls_svd_get_profile (LS_Filter_SVD
+                             on device);
+                             660: prc_firdec_desc, prc_fir_decimate, prc_shift, prc_normalize_workspace_bytes, prc_normalize (the rest of
                              signal_utils.py on device: decimate, channel_preprocessing, shift, offset_compensation, normalize);
                              650: prc_welch_desc, prc_welch_rows, prc_welch_workspace_bytes, prc_welch (Welch spectra on device: the psd, csd and
                              specgram of signal_preview.py);
@@ -280,6 +282,41 @@ int prc_nlms_execute(const void* ref, const void* srv, int64_t n, int64_t stride
                      int32_t filter_len, int32_t peek, float mu, const void* taps_in,
                      void* out, int64_t out_stride, void* taps_out, int32_t nstreams,
                      void* stream);
+
+/* ---- LS_Filter_SVD (clutter_removal.py:58-107) ------------------------------------------ */
+/* nblocks independent truncated-SVD block least-squares cancellers on the circulant data matrix A[:, k] = roll(ref, k - peek),
+ * T = filter_len + peek columns: h = V S^+ U^H srv, out = srv - A h (complex64).  Computed from the Gram matrix A^H A (the
+ * Hermitian Toeplitz matrix of the circular autocorrelation, accumulated in float64) by one-sided Jacobi in float64; no
+ * N x T matrix is formed.  Block b reads ref and srv at b*stride and writes out at b*out_stride.
+ * Cut rule: a singular value is dropped when sigma < max(1e-10, rcond * sigma_max).  rcond < 0 selects the default
+ * 4 sqrt(T) 2^-26 (lambda below 16 T 2^-52 lambda_max: what a Gram matrix accumulated in float64 cannot tell from its own
+ * rounding); rcond = 0 is the reference's absolute rule alone; rcond must be below 1.
+ * taps_out: optional complex128 [nblocks][T]; sv_out: optional double [nblocks][T], the singular values of A in descending
+ * order; info_out: optional int32 [nblocks][3] = directions kept, Jacobi sweeps run (the last one without a rotation
+ * included), 1 if the block converged within the cap of 30 sweeps, else 0 (its results are then those of the last sweep).
+ * out = (srv - A hi) - A lo with h = hi + lo, hi the float32-representable part of h: the circular FIR kernel of
+ * prc_ls_execute, which carries float32 taps, twice.
+ * workspace: prc_ls_svd_workspace_bytes(n, filter_len, peek, nblocks) bytes of device memory, 16-byte aligned, owned by the
+ * caller and not shared by calls in flight; nothing in it needs initialising (about 32 T^2 + 8 n bytes per block plus the
+ * correlation partials).
+ * The call does not allocate device memory.  It DOES synchronise: the host reads the rotation counters back once per sweep
+ * (stream synchronisation) and stops at the first sweep without rotations, so the call cannot be captured into a graph; it
+ * returns with the sweeps complete and the last kernels (taps, FIR) enqueued on `stream`.  Results are bit-identical from
+ * run to run and do not depend on which other blocks share the call.
+ * Limits: 1 <= T < n, T <= 4096, stride and out_stride >= n.  Anything else, a null ref / srv / out / workspace or a
+ * misaligned workspace: PRC_EINVAL. */
+int prc_ls_svd_workspace_bytes(int64_t n, int32_t filter_len, int32_t peek, int32_t nblocks, size_t* bytes);
+int prc_ls_svd_execute(const void* ref, const void* srv, int64_t n, int64_t stride, int32_t filter_len, int32_t peek,
+                       double rcond /* < 0: the default above */, int32_t nblocks, void* out, int64_t out_stride,
+                       void* taps_out /* c128 [nblocks][T] or NULL */, double* sv_out /* [nblocks][T] or NULL */,
+                       int32_t* info_out /* [nblocks][3]: kept, sweeps, converged; or NULL */,
+                       void* workspace, void* stream);
+/* Stage timing for tools/ls_svd_bench.py, process-wide: while enabled, every prc_ls_svd_execute records events around its
+ * stages and waits for its last kernel; get_profile returns the last call's milliseconds for correlate (float64
+ * correlations and their reduction), jacobi (Gram set-up, the sweeps and their counter read-backs), taps (eigenvalues, cut,
+ * taps) and apply (the FIR), and the number of sweeps launched. */
+int prc_ls_svd_set_profiling(int32_t enable);
+int prc_ls_svd_get_profile(double* ms /* [4] */, int32_t* sweeps);
 
 /* ---- GAL_JPE (clutter_removal.py:251-365) --------------------------------------------- */
 /* nstreams independent gradient-adaptive-lattice joint-process estimators: lattice_len reflection coefficients k, then a

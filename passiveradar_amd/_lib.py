@@ -131,7 +131,7 @@ PERSISTENCE_TERMS_PER_LAUNCH = 256
 DISPLAY_PLOT, DISPLAY_STORED = 0, 1   # prc_display_orient
 
 
-MIN_LIB_VERSION = 660      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+MIN_LIB_VERSION = 670      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -179,6 +179,12 @@ _SIGNATURES = {
     "prc_gal_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p]),
+    "prc_ls_svd_workspace_bytes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_ls_svd_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                     C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "prc_ls_svd_set_profiling": (C.c_int, [C.c_int32]),
+    "prc_ls_svd_get_profile": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "prc_frontend_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(FrontendDesc)]),
     "prc_frontend_plan_destroy": (C.c_int, [C.c_void_p]),
     "prc_frontend_out_len": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -1,9 +1,10 @@
 """Drop-in for the clutter filters of the reference's ``passiveRadar/clutter_removal.py`` that
 are on the north-star path: LS_Filter (:6-56), LS_Filter_Toeplitz (:109-160),
-LS_Filter_Multiple (:162-187), NLMS_filter (:189-249), and GAL_JPE (:251-365).  Same signatures,
-return dtypes and ValueError on mismatched inputs; the arithmetic runs in libprcore.so (complex64
-streams, complex128 Levinson solve on device).  LS_Filter_SVD is not on the path (never called by
-the reference) and is deliberately absent.
+LS_Filter_Multiple (:162-187), NLMS_filter (:189-249), and GAL_JPE (:251-365), and for LS_Filter_SVD
+(:58-107), which the reference never calls itself.  Same signatures, return dtypes and ValueError on
+mismatched inputs; the arithmetic runs in libprcore.so (complex64 streams, complex128 Levinson solve
+on device).  LS_Filter_SVD is the truncated-SVD form through the float64 Gram matrix of the circulant
+data matrix (csrc/ls_svd.hip); it adds a relative cut ``rcond`` to the reference's absolute one.
 """
 from __future__ import annotations
 
@@ -11,7 +12,8 @@ import numpy as np
 
 from . import _lib, engine
 
-__all__ = ["LS_Filter", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "NLMS_filter", "GAL_JPE", "set_default_ls_method"]
+__all__ = ["LS_Filter", "LS_Filter_SVD", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "NLMS_filter", "GAL_JPE",
+           "set_default_ls_method"]
 
 _LS_METHOD = {"m": 0}     # 0 auto | 1 time-domain kernels | 2 FFT kernels (tests flip it)
 
@@ -73,6 +75,47 @@ def LS_Filter(refChannel, srvChannel, filterLen, reg=1.0, peek=10, return_filter
     out, taps = _ls_run(refChannel, srvChannel, filterLen, peek, True, 1.0, (0.0,), float(reg),
                         return_filter)
     return (out, taps.astype(np.complex64)) if return_filter else out
+
+
+def LS_Filter_SVD(refChannel, srvChannel, filterLen, peek=10, return_filter=False, *, rcond=None,
+                  return_singular_values=False):
+    """Block LS canceller by truncated SVD (:58-107) without forming the N x T matrix of circular shifts A: its Gram
+    matrix is the circular-autocorrelation Toeplitz matrix, accumulated in float64 and diagonalised by one-sided Jacobi
+    in float64 on the GPU; h = V S^+ U^H srv, out = srv - A h.  complex64 out and taps, like the reference.
+
+    Cut rule: a singular value is dropped when sigma < max(1e-10, rcond * sigma_max).  The reference has the absolute
+    1e-10 alone, which its own float32 SVD rarely reaches: on a band-limited reference it inverts singular values of
+    1e-8 sigma_max and returns noise.  ``rcond=None`` is 4 sqrt(T) 2^-26 with T = filterLen + peek (3.0e-7 at 26 taps):
+    what a Gram matrix accumulated in float64 cannot tell from its own rounding.  ``rcond=0`` is the reference's rule.
+
+    Returns out, then the taps with ``return_filter``, then the singular values of A (float64, descending) with
+    ``return_singular_values``.  Raises PrcoreError if the Jacobi sweeps did not converge within their cap (30)."""
+    _check_same(refChannel, srvChannel)
+    ref = np.ascontiguousarray(refChannel, dtype=np.complex64).reshape(-1)
+    srv = np.ascontiguousarray(srvChannel, dtype=np.complex64).reshape(-1)
+    n = ref.shape[0]
+    T = int(filterLen) + int(peek)
+    wsb = engine.ls_svd_workspace_bytes(n, filterLen, peek, 1)      # the size limits (1 <= T < n, T <= 4096): ValueError
+    st = engine.staging()
+    d_ref = st.get("svd_ref", 8 * n)
+    d_srv = st.get("svd_srv", 8 * n)
+    d_out = st.get("svd_out", 8 * n)
+    d_taps = st.get("svd_taps", 16 * T)
+    d_sv = st.get("svd_sv", 8 * T)
+    d_info = st.get("svd_info", 12)
+    d_ws = st.get("svd_ws", wsb)
+    d_ref.upload(ref)
+    d_srv.upload(srv)
+    engine.ls_svd_execute(d_ref, d_srv, d_out, n, filterLen, peek, rcond, 1, n, n, d_taps, d_sv, d_info, d_ws)
+    kept, sweeps, converged = (int(v) for v in d_info.download((3,), np.int32))
+    if not converged:
+        raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, f"LS_Filter_SVD: the Jacobi sweeps did not converge within {sweeps} sweeps")
+    res = [d_out.download((n,), np.complex64).reshape(np.shape(srvChannel))]
+    if return_filter:
+        res.append(d_taps.download((T,), np.complex128).astype(np.complex64))
+    if return_singular_values:
+        res.append(d_sv.download((T,), np.float64))
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def NLMS_filter(refChannel, srvChannel, filterLen, mu, peek=10, initialTaps=None, returnFilter=False):

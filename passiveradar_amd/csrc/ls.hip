@@ -1040,6 +1040,32 @@ static int fir_tile(int T) {
 }
 static size_t fir_lds(int T) { const size_t t = (size_t)fir_tile(T); return sizeof(float2) * (t + FIR_SPAN + t - 1); }
 
+// out = srv - A taps for the circulant data matrix of LS_Filter / LS_Filter_SVD (ls_svd.hip): fir_subtract_kernel with
+// circular = 1 and no Doppler rotation, taps [nblocks][T] complex128 (rounded to float32 by the kernel)
+int ls_launch_fir_circular(const float2* ref, const float2* srv, float2* out, const double2* taps, int64_t ref_stride,
+                           int64_t srv_stride, int64_t out_stride, int64_t n, int T, int peek, int nblocks, hipStream_t stream) {
+    FirArgs fa;
+    fa.ref = ref;
+    fa.srv = srv;
+    fa.out = out;
+    fa.taps = taps;
+    fa.ref_stride = ref_stride;
+    fa.srv_stride = srv_stride;
+    fa.out_stride = out_stride;
+    fa.n = n;
+    fa.T = T;
+    fa.peek = peek;
+    fa.circular = 1;
+    fa.rot = 0;
+    fa.pr = PhaseRamp{0.f, 0.f, 0.f, 0};
+    fa.tile = fir_tile(T);
+    { const int rc = prc_lds_optin(reinterpret_cast<const void*>(&fir_subtract_kernel), 160 * 1024); if (rc) return rc; }
+    hipLaunchKernelGGL(fir_subtract_kernel, dim3((unsigned)ceil_div64(n, FIR_SPAN), (unsigned)nblocks), dim3(LS_THREADS),
+                       fir_lds(T), stream, fa);
+    PRC_LAUNCH_CHECK();
+    return PRC_OK;
+}
+
 // allow_cache = false: the retry after a mandatory allocation failed while the (optional) spectrum cache was held --
 // the same plan without the cache, i.e. on the kernels that recompute the spectra
 static int ls_plan_create_impl(prc_ls_plan** plan, const prc_ls_desc* d, bool allow_cache) {

@@ -30,6 +30,10 @@ struct LsFftArgs {
     float2 gamma_m1;
 };
 
+// time-domain FIR of ls.hip on the circulant data matrix: out = srv - A taps (taps [nblocks][T] complex128, which the kernel
+// rounds to float32)
+int ls_launch_fir_circular(const float2* ref, const float2* srv, float2* out, const double2* taps, int64_t ref_stride,
+                           int64_t srv_stride, int64_t out_stride, int64_t n, int T, int peek, int nblocks, hipStream_t stream);
 bool ls_fft_supported(int T);
 int ls_fft_waves_per_block(int64_t n, int T);
 int ls_launch_corr_fft(LsFftArgs a, double theta, int waves_per_block, int nblocks, bool with_autocorr,

@@ -302,6 +302,37 @@ def gal_execute(ref, srv, out, n, lattice_len, delay_len, mu1, mu2, peek=10, k_o
                                 _ptr(workspace), stream))
 
 
+def ls_svd_workspace_bytes(n, filter_len, peek=10, nblocks=1):
+    """device bytes prc_ls_svd_execute needs for ``nblocks`` blocks of ``n`` samples and filter_len + peek taps"""
+    nb = C.c_size_t(0)
+    check(lib().prc_ls_svd_workspace_bytes(int(n), int(filter_len), int(peek), int(nblocks), C.byref(nb)))
+    return int(nb.value)
+
+
+def ls_svd_execute(ref, srv, out, n, filter_len, peek=10, rcond=None, nblocks=1, stride=None, out_stride=None,
+                   taps_out=None, sv_out=None, info_out=None, workspace=None, stream=None):
+    """LS_Filter_SVD over ``nblocks`` independent blocks (device buffers or torch tensors).  ``rcond``: None = the default
+    cut 4 sqrt(T) 2^-26 (include/prcore.h).  ``taps_out`` complex128 [nblocks][T], ``sv_out`` float64 [nblocks][T],
+    ``info_out`` int32 [nblocks][3] (kept, sweeps, converged); ``workspace``: ls_svd_workspace_bytes(...) device bytes.
+    Synchronises ``stream`` once per Jacobi sweep."""
+    check(lib().prc_ls_svd_execute(_ptr(ref), _ptr(srv), int(n), int(n if stride is None else stride), int(filter_len),
+                                   int(peek), -1.0 if rcond is None else float(rcond), int(nblocks), _ptr(out),
+                                   int(n if out_stride is None else out_stride), _ptr(taps_out), _ptr(sv_out),
+                                   _ptr(info_out), _ptr(workspace), stream))
+
+
+def ls_svd_set_profiling(enable=True):
+    check(lib().prc_ls_svd_set_profiling(int(bool(enable))))
+
+
+def ls_svd_get_profile():
+    """((ms_correlate, ms_jacobi, ms_taps, ms_apply), sweeps launched) of the last ls_svd_execute under set_profiling"""
+    ms = (C.c_double * 4)()
+    k = C.c_int32()
+    check(lib().prc_ls_svd_get_profile(ms, C.byref(k)))
+    return tuple(ms), k.value
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

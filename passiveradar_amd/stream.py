@@ -378,17 +378,21 @@ class HipBackend:
     """
 
     LS_HALO = 2        # spare blocks in every LS plan (the two halo chunks of a sharded stream)
+    CLUTTER_MODES = ("ls", "ls_direct", "ls_svd", "nlms", "gal", None)
 
     def __init__(self, cpi_samples, num_range_cells, num_doppler_cells, IF_sample_rate,
                  doppler_bins=(0, 1, -1, 2, -2), window=("kaiser", 5.0), clutter="ls",
                  batch=16, device=None, caf_method=0, doppler_method=0, nlms_mu=0.02, overlap=True,
                  ls_method=0, nsub=1, ls_streams=3, nref=1, ls_reg=1.0, caf_multi="auto", caf_lanes=1,
-                 gal_lattice=8, gal_mu=(1e-3, 1e-2)):
+                 gal_lattice=8, gal_mu=(1e-3, 1e-2), ls_rcond=None):
         """clutter: "ls" = LS_Filter_Multiple over ``doppler_bins`` (main.py:169-176, the reference's choice),
         "ls_direct" = LS_Filter (clutter_removal.py:6-56: circular data matrix, ``ls_reg`` on the Gram diagonal, one
         bin -- SURVEY 8's config-2 "LS_Filter variant"), "nlms" = NLMS_filter with step ``nlms_mu``, "gal" = GAL_JPE
         (clutter_removal.py:251-365) with ``gal_lattice`` reflection coefficients, a delay line of R taps and peek 10 (the
-        lengths "nlms" uses) and steps ``gal_mu`` = (mu1, mu2), None = no canceller.  The GAL defaults: (1e-3, 1e-2) are the
+        lengths "nlms" uses) and steps ``gal_mu`` = (mu1, mu2), "ls_svd" = LS_Filter_SVD (clutter_removal.py:58-107:
+        the circular data matrix of "ls_direct", truncated SVD with the relative cut ``ls_rcond``, None = its default; one
+        block per hop chunk, every chunk in one call, which synchronises the stream once per Jacobi sweep), None = no
+        canceller.  The GAL defaults: (1e-3, 1e-2) are the
         ballpark step sizes of the reference's docstring, and 8 reflection coefficients (at most 64 take the faster row
         form of the kernel) are enough to whiten AR-like FM / OFDM spectra.  GAL restarts on every hop chunk, as the
         reference's per-chunk filters do, and at these steps it does NOT converge within a chunk on strong clutter: on the
@@ -405,7 +409,7 @@ class HipBackend:
         self.R, self.F = int(num_range_cells), int(num_doppler_cells)
         self.fs = float(IF_sample_rate)
         self.bins = tuple(float(b) for b in doppler_bins)
-        if clutter not in ("ls", "ls_direct", "nlms", "gal", None):
+        if clutter not in self.CLUTTER_MODES:
             raise ValueError(f"HipBackend: unknown clutter canceller {clutter!r}")
         self.clutter = clutter
         self.ls_like = clutter in ("ls", "ls_direct")       # block least-squares cancellers: plans, sub-batches, chains
@@ -418,6 +422,8 @@ class HipBackend:
         if clutter == "gal" and not 1 <= self.gal_lattice <= self.R:
             raise ValueError(f"HipBackend: gal_lattice must be in [1, {self.R}] (the delay line is R taps), got {gal_lattice}")
         self._gal_ws = None
+        self.ls_rcond = None if ls_rcond is None else float(ls_rcond)
+        self._svd_ws = None
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # LS launches of batch/nsub chunks.  Measured on MI355X (config 2, two LS chains in flight): 256-chunk launches
         # (nsub = 1) 20.45 k frames/s, 128-chunk launches (nsub = 2) 19.56 k -- the latency-bound Durbin / solve kernels
@@ -556,6 +562,16 @@ class HipBackend:
         elif self.clutter == "ls_direct":
             (plan or self.ls).execute(ref_pad[off:], srv_pad[off:], out[off:], nb, C, C, self.fs, (0.0,), self.ls_reg,
                                       None, stream)
+        elif self.clutter == "ls_svd":
+            wsb = self.engine.ls_svd_workspace_bytes(C, self.R, 10, nb)
+            if self._svd_ws is None or self._svd_ws.numel() < wsb:
+                self._svd_ws = self.torch.empty(wsb, dtype=self.torch.uint8, device=self.device)
+            info = self.torch.empty((nb, 3), dtype=self.torch.int32, device=self.device)
+            self.engine.ls_svd_execute(ref_pad[off:], srv_pad[off:], out[off:], C, self.R, 10, self.ls_rcond, nb, C, C,
+                                       None, None, info, self._svd_ws, stream)
+            if not bool(info[:, 2].all()):
+                from . import _lib
+                raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, "HipBackend: LS_Filter_SVD did not converge on every chunk")
         elif self.clutter == "gal":
             wsb = self.engine.gal_workspace_bytes(self.R, nb)
             ws = None
