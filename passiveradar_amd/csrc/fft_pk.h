@@ -8,8 +8,8 @@
 //   a * t, a * conj(t)                   two (mul + fma), against four scalar ones
 //   w += conj(u) v                       two fma, against four
 // The radix-16 butterfly below is 80 packed instructions against 160 scalar ones for the same roundings in the
-// same order (every result is bit-identical to the scalar dft16 of fft_wave.h; tools/ubench/dft16pk.hip checks that
-// on the device).  SLP vectorisation of the scalar code does not get there: it makes v_pk_add/mul only for the
+// same order (every result is bit-identical to the scalar dft16 of fft_wave.h; tests/test_gpu_fft_forms.py checks that
+// on the device, primitive by primitive and for the whole transforms).  SLP vectorisation of the scalar code does not get there: it makes v_pk_add/mul only for the
 // unswizzled cases and pays v_mov pairs for the rest (round 1 measured that as "no gain, more registers").
 #pragma once
 #include "fft_wave.h"
