@@ -263,15 +263,10 @@ static int64_t surf_elems(const prc_caf_plan* p) {
     return (int64_t)p->desc.freq_bins * (p->desc.range_bins + 1);
 }
 
-// segment sums of frames [f0, f0 + nf) of one reference channel into the plan's slow-time buffer, surfaces s0...
-static int run_segments(prc_caf_plan* p, const void* ref, const void* srv, int64_t frame_stride,
-                        int64_t n_valid, const float* window, int f0, int nf, int s0, hipStream_t stream) {
-    PRC_REQUIRE(ref && srv, PRC_EINVAL, "prc_caf_execute: null input");
-    PRC_REQUIRE(n_valid >= 0 && n_valid <= p->desc.n, PRC_ESHAPE,
-                "prc_caf_execute: n_valid=%lld exceeds inputLen=%lld", (long long)n_valid,
-                (long long)p->desc.n);
-    CafSegArgs a;
-    a.ref = (const float2*)ref + (int64_t)f0 * frame_stride;
+// everything of the segment kernels' argument block but ref, y and y_layout, for frames f0... of srv
+static CafSegArgs seg_args(const prc_caf_plan* p, const void* srv, int64_t frame_stride, int64_t n_valid,
+                           const float* window, int f0) {
+    CafSegArgs a{};
     a.srv = (const float2*)srv + (int64_t)f0 * frame_stride;
     a.window = window;
     a.taps = p->d_taps;
@@ -286,6 +281,29 @@ static int run_segments(prc_caf_plan* p, const void* ref, const void* srv, int64
     a.freq_bins = p->desc.freq_bins;
     a.y_kt = p->y_kt;
     a.y_surface = p->y_surf;
+    return a;
+}
+
+// body(f0, nf) over frames [0, nframes) in groups of g (at least one); stops at the first error
+template <class Body>
+static int for_frame_groups(int nframes, int g, Body body) {
+    if (g < 1) g = 1;
+    for (int f0 = 0; f0 < nframes; f0 += g) {
+        const int nf = nframes - f0 < g ? nframes - f0 : g;
+        if (int rc = body(f0, nf)) return rc;
+    }
+    return PRC_OK;
+}
+
+// segment sums of frames [f0, f0 + nf) of one reference channel into the plan's slow-time buffer, surfaces s0...
+static int run_segments(prc_caf_plan* p, const void* ref, const void* srv, int64_t frame_stride,
+                        int64_t n_valid, const float* window, int f0, int nf, int s0, hipStream_t stream) {
+    PRC_REQUIRE(ref && srv, PRC_EINVAL, "prc_caf_execute: null input");
+    PRC_REQUIRE(n_valid >= 0 && n_valid <= p->desc.n, PRC_ESHAPE,
+                "prc_caf_execute: n_valid=%lld exceeds inputLen=%lld", (long long)n_valid,
+                (long long)p->desc.n);
+    CafSegArgs a = seg_args(p, srv, frame_stride, n_valid, window, f0);
+    a.ref = (const float2*)ref + (int64_t)f0 * frame_stride;
     const int64_t off = (int64_t)s0 * p->y_surf;
     if (p->method == PRC_CAF_FFT || p->method == PRC_CAF_FFT4096) {
         // the FFT kernels write whole rows y[j][0..R] (coalesced)
@@ -348,15 +366,11 @@ extern "C" int prc_caf_execute(prc_caf_plan* p, const void* ref, const void* srv
     if (rc) return rc;
     PRC_REQUIRE(out, PRC_EINVAL, "prc_caf_execute: null output");
     std::lock_guard<std::mutex> lk(p->mtx);
-    const int g = p->doppler == PRC_DOPPLER_COLUMN ? p->group : nframes;
-    for (int f0 = 0; f0 < nframes; f0 += g) {
-        const int nf = nframes - f0 < g ? nframes - f0 : g;
-        rc = run_segments(p, ref, srv, frame_stride, n_valid, window, f0, nf, f0, (hipStream_t)stream);
+    return for_frame_groups(nframes, p->doppler == PRC_DOPPLER_COLUMN ? p->group : nframes, [&](int f0, int nf) -> int {
+        int rc = run_segments(p, ref, srv, frame_stride, n_valid, window, f0, nf, f0, (hipStream_t)stream);
         if (rc) return rc;
-        rc = run_doppler(p, (float2*)out + (int64_t)f0 * surf_elems(p), f0, nf, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return PRC_OK;
+        return run_doppler(p, (float2*)out + (int64_t)f0 * surf_elems(p), f0, nf, (hipStream_t)stream);
+    });
 }
 
 // fast_xambg for nref reference channels against ONE surveillance channel (range_doppler_processing.py:12-90 once
@@ -382,83 +396,46 @@ extern "C" int prc_caf_execute_multi(prc_caf_plan* p, const void* const* refs_ho
     const int per = p->multi == PRC_CAF_MULTI_SHARED ? nref : (p->multi == PRC_CAF_MULTI_PAIRS ? 2 : 1);
     const bool shared = per > 1 && p->method == PRC_CAF_FFT4096 && p->doppler == PRC_DOPPLER_COLUMN && nref > 1 &&
                         caf_team_multi_supported(p->desc.n, p->desc.range_bins, p->desc.freq_bins, p->ntaps, per);
+    // Doppler transform of every channel's surfaces of a group of nf frames in one launch: surface (i, b) at [i * nf + b]
+    // of the workspace
+    auto doppler_all = [&](int f0, int nf) -> int {
+        float2* outs[PRC_CAF_MAX_REFS];
+        for (int i = 0; i < nref; ++i) outs[i] = (float2*)outs_host[i] + (int64_t)f0 * se;
+        return dop_launch_multi(p->d_y2, p->y_surf, (int64_t)nf * p->y_surf, outs, nref, p->d_dop_tw, p->desc.freq_bins,
+                                p->desc.range_bins + 1, nf, st);
+    };
     if (!shared && nref > 1 && p->method == PRC_CAF_FFT4096 && p->doppler == PRC_DOPPLER_COLUMN) {
         // "turns" in ONE launch per stage: the single-reference kernel with the illuminator as a third grid dimension, then the
         // Doppler kernel over every channel's surfaces -- nothing shared, but no tail of nref small launches (config 5, 16
         // frames: 10.7 rounds of workgroups per segment launch and 8.03 per Doppler launch, each rounded up, become 42.7 and 32.1)
-        int g = p->group / nref;
-        if (g < 1) g = 1;
-        for (int f0 = 0; f0 < nframes; f0 += g) {
-            const int nf = nframes - f0 < g ? nframes - f0 : g;
-            CafSegArgs a;
-            a.ref = nullptr;
-            a.srv = (const float2*)srv + (int64_t)f0 * frame_stride;
-            a.window = window;
-            a.taps = nullptr;
-            a.taps_rev = nullptr;
+        return for_frame_groups(nframes, p->group / nref, [&](int f0, int nf) -> int {
+            CafSegArgs a = seg_args(p, srv, frame_stride, n_valid, window, f0);
             a.y = p->d_y2;
-            a.frame_stride = frame_stride;
-            a.n = p->desc.n;
-            a.n_valid = n_valid;
-            a.q = p->q;
-            a.ntaps = p->ntaps;
-            a.half = p->half;
-            a.range_bins = p->desc.range_bins;
-            a.freq_bins = p->desc.freq_bins;
             a.y_layout = PRC_Y_JK;
-            a.y_kt = p->y_kt;
-            a.y_surface = p->y_surf;
             const float2* refs[PRC_CAF_MAX_REFS];
-            float2* outs[PRC_CAF_MAX_REFS];
-            for (int i = 0; i < nref; ++i) {
-                refs[i] = (const float2*)refs_host[i] + (int64_t)f0 * frame_stride;
-                outs[i] = (float2*)outs_host[i] + (int64_t)f0 * se;
-            }
+            for (int i = 0; i < nref; ++i) refs[i] = (const float2*)refs_host[i] + (int64_t)f0 * frame_stride;
             int rc = caf_launch_fft_team_refs(a, refs, nref, (int64_t)nf * p->y_surf, nf, st);
             if (rc) return rc;
-            rc = dop_launch_multi(p->d_y2, p->y_surf, (int64_t)nf * p->y_surf, outs, nref, p->d_dop_tw, p->desc.freq_bins,
-                                  p->desc.range_bins + 1, nf, st);
-            if (rc) return rc;
-        }
-        return PRC_OK;
+            return doppler_all(f0, nf);
+        });
     }
     if (!shared) {
         // one pass per illuminator (any method): same results, nothing shared
         for (int i = 0; i < nref; ++i) {
-            const int g = p->doppler == PRC_DOPPLER_COLUMN ? p->group : nframes;
-            for (int f0 = 0; f0 < nframes; f0 += g) {
-                const int nf = nframes - f0 < g ? nframes - f0 : g;
+            int rc = for_frame_groups(nframes, p->doppler == PRC_DOPPLER_COLUMN ? p->group : nframes, [&](int f0, int nf) -> int {
                 int rc = run_segments(p, refs_host[i], srv, frame_stride, n_valid, window, f0, nf, f0, st);
                 if (rc) return rc;
-                rc = run_doppler(p, (float2*)outs_host[i] + (int64_t)f0 * se, f0, nf, st);
-                if (rc) return rc;
-            }
+                return run_doppler(p, (float2*)outs_host[i] + (int64_t)f0 * se, f0, nf, st);
+            });
+            if (rc) return rc;
         }
         return PRC_OK;
     }
-    // frames in groups of g: surface (i, b) of a group at [i * nf + b] of the workspace; the surveillance pieces of a
-    // segment are transformed once per launch for the `per` illuminators it carries
-    int g = p->group / nref;
-    if (g < 1) g = 1;
-    for (int f0 = 0; f0 < nframes; f0 += g) {
-        const int nf = nframes - f0 < g ? nframes - f0 : g;
-        CafSegArgs a;
-        a.ref = nullptr;
-        a.srv = (const float2*)srv + (int64_t)f0 * frame_stride;
-        a.window = window;
-        a.taps = nullptr;
-        a.taps_rev = nullptr;
-        a.frame_stride = frame_stride;
-        a.n = p->desc.n;
-        a.n_valid = n_valid;
-        a.q = p->q;
-        a.ntaps = p->ntaps;
-        a.half = p->half;
-        a.range_bins = p->desc.range_bins;
-        a.freq_bins = p->desc.freq_bins;
+    // frames in groups: the surveillance pieces of a segment are transformed once per launch for the `per` illuminators it
+    // carries
+    return for_frame_groups(nframes, p->group / nref, [&](int f0, int nf) -> int {
+        CafSegArgs a = seg_args(p, srv, frame_stride, n_valid, window, f0);
         a.y_layout = PRC_Y_JK;
-        a.y_kt = p->y_kt;
-        a.y_surface = p->y_surf;
         for (int i0 = 0; i0 < nref; i0 += per) {
             const int k = nref - i0 < per ? nref - i0 : per;
             const float2* refs[PRC_CAF_MAX_REFS];
@@ -467,11 +444,6 @@ extern "C" int prc_caf_execute_multi(prc_caf_plan* p, const void* const* refs_ho
             int rc = caf_launch_fft_team_multi(a, refs, k, (int64_t)nf * p->y_surf, nf, st);
             if (rc) return rc;
         }
-        float2* outs[PRC_CAF_MAX_REFS];
-        for (int i = 0; i < nref; ++i) outs[i] = (float2*)outs_host[i] + (int64_t)f0 * se;
-        int rc = dop_launch_multi(p->d_y2, p->y_surf, (int64_t)nf * p->y_surf, outs, nref, p->d_dop_tw, p->desc.freq_bins,
-                                  p->desc.range_bins + 1, nf, st);
-        if (rc) return rc;
-    }
-    return PRC_OK;
+        return doppler_all(f0, nf);
+    });
 }

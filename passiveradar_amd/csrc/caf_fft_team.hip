@@ -23,7 +23,7 @@
 #endif
 #include "caf_internal.h"
 #include "fft_team.h"
-#include "caf_team_tail.h"
+#include "caf_team.h"
 #include <math.h>
 
 void ft_make_tables(float2* t) {
@@ -65,34 +65,8 @@ template <bool HAS_WIN>
 __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_kernel(CafTeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* lds = reinterpret_cast<float2*>(smem_raw);
-    // Workgroup -> work.  Workgroups reach the eight XCDs round-robin in launch order and every XCD has its own L2: workgroup
-    // L (XCD L & 7, slot L >> 3 there) takes channel (L >> 3) % nref of chunk 8 ((L >> 3) / nref) + (L & 7).  The channels of
-    // a multi-illuminator frame read the SAME surveillance windows and sit in consecutive slots of ONE XCD: one of them
-    // fetches a window from HBM, the others find it in that XCD's L2 (config 5, four channels: 219 -> 96 MB fetched per
-    // surface, 301 -> 281 us per frame).  Chunks themselves keep going round the XCDs: giving every XCD a contiguous run of
-    // segments instead (PRC_OPT_CAF_XCD_CONTIG = 1; neighbouring segments share half a window) measured 3-6 % SLOWER at
-    // one channel and at four, configs 3 and 5 alike (profiles/r04_ab_log.md, call 12) -- eight distant streams instead of
-    // one; it is the option's off position that ships.
-    const int per_xcd = (a.nchunks + 7) >> 3;
-    const int slot = (int)(blockIdx.x >> 3);
-    const int ch = slot % a.nref, ci = slot / a.nref;
-    int b, bx;
-    if (a.pair_half > 0) {
-        // 50 %-overlapped frames: position A of the stream (in chunks of half a frame) is covered by frame A / half (its
-        // first half) and by the frame before (its second half) -- the two take consecutive slots, like the channels, and
-        // share the reference and surveillance samples through the L2 (config 5, 16 frames: 285 -> 276 us per four-
-        // illuminator frame, 74 -> 72.4 us per surface at one channel; config 3: no difference)
-        const int k = ci & 1, A = (ci >> 1) * 8 + (int)(blockIdx.x & 7u);
-        if (A >= (a.nframes + 1) * a.pair_half) return;         // uniform, before any barrier
-        b = A / a.pair_half - k;
-        bx = A % a.pair_half + k * a.pair_half;
-        if (b < 0 || b >= a.nframes || bx >= a.chunks_x) return;
-    } else {
-        const int chunk = a.xcd_contig ? (int)(blockIdx.x & 7u) * per_xcd + ci : ci * 8 + (int)(blockIdx.x & 7u);
-        if (ci >= per_xcd || chunk >= a.nchunks) return;        // uniform, before any barrier
-        b = chunk / a.chunks_x;
-        bx = chunk - b * a.chunks_x;
-    }
+    int ch, b, bx;
+    if (!caft_work(a, &ch, &b, &bx)) return;
     const float2* __restrict__ ref = a.refs[ch] + (int64_t)b * a.s.frame_stride;
     const float2* __restrict__ srv = a.s.srv + (int64_t)b * a.s.frame_stride;
     const float* __restrict__ win = a.s.window;
@@ -104,21 +78,12 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
     const int R = a.s.range_bins;
     const int B = a.piece, LB = a.lagblk;
     const unsigned vo8 = (unsigned)t * 8u, vo4 = (unsigned)t * 4u;
-    auto clampu = [](int x) { return x < 0 ? 0u : (unsigned)x; };
-    const float sc = 1.0f / (float)FT_P;
 
     for (int sg = 0; sg < a.segs; ++sg) {
         const int64_t j = (int64_t)bx * a.segs + sg;
         if (j >= a.s.freq_bins) break;                         // uniform
-        const int64_t n_hi64 = j * a.s.q + a.s.half;
-        const int64_t n_lo64 = n_hi64 - (a.s.ntaps - 1);
-        const int lo = n_lo64 < 0 ? 0 : (int)n_lo64;
-        const int hi = n_hi64 > N - 1 ? N - 1 : (int)n_hi64;
-        // a short remainder after the last full piece goes the direct way
-        const int len = hi - lo + 1;
-        int tail = len % B;
-        if (tail > CAFT_TAIL_MAX || len < B) tail = 0;
-        const int hi_f = hi - tail;                            // last sample that goes through the transforms
+        const CaftSeg seg = caft_segment(a.s, j, N, B);
+        const int lo = seg.lo, hi_f = seg.hi_f, tail = seg.tail;
 
         for (int lb = 0; lb < a.nlagblk; ++lb) {
             float2 acc[16];
@@ -129,47 +94,19 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
             // exist" (zero padding of U, ragged last piece, n_valid < n).
             float2 un[16];
             float wn[16];
-            auto issue_u = [&](int n0, int nz = 16) {
+            // registers beyond the piece (r >= NZ: 256 r >= cnt) are zero for every thread: not even loaded
+            auto issue_u = [&](auto nzc, int n0) {
+                constexpr int NZ = decltype(nzc)::value;
                 const int rem = hi_f - n0 + 1;
                 int cnt = rem < B ? rem : B;
                 if (NV - n0 < cnt) cnt = NV - n0;
-                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, clampu(cnt) * 8u);
-                // registers beyond the piece (r >= nz: 256 r >= cnt) are zero for every thread: not even loaded
+                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, caft_clampu(cnt) * 8u);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    if (r < 8 || (r < 12 && nz > 8) || nz > 12) un[r] = prc_buf_load_c64(ru, vo8, 2048u * r);
-                    else un[r] = make_float2(0.f, 0.f);
-                }
+                for (int r = 0; r < NZ; ++r) un[r] = prc_buf_load_c64(ru, vo8, 2048u * r);
                 if (HAS_WIN) {
-                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, clampu(cnt) * 4u);
+                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, caft_clampu(cnt) * 4u);
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        if (r < 8 || (r < 12 && nz > 8) || nz > 12) wn[r] = prc_buf_load_f32(rw, vo4, 1024u * r);
-                        else wn[r] = 0.f;
-                    }
-                }
-            };
-            // srv slots [0, cnt+LB-1) of this lag block: frame offsets start .. with circular wrap (:82)
-            auto issue_v = [&](float2 (&v)[16], int n0, int cnt) {
-                int start = n0 + lb * LB;
-                if (start >= N) start -= N;
-                const int want = cnt + LB - 1;
-                int c1 = want;
-                if (N - start < c1) c1 = N - start;
-                if (NV - start < c1) c1 = NV - start;
-                const __amdgpu_buffer_rsrc_t rv = prc_rsrc(srv + start, clampu(c1) * 8u);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = prc_buf_load_c64(rv, vo8, 2048u * r);
-                const int over = start + want - N;              // slots that wrapped (uniform, rare)
-                if (over > 0) {
-                    const __amdgpu_buffer_rsrc_t rw2 = prc_rsrc(srv, clampu(over < NV ? over : NV) * 8u);
-                    const unsigned voff = vo8 - (unsigned)(N - start) * 8u;   // threads before the wrap: out of range
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float2 w2 = prc_buf_load_c64(rw2, voff + 2048u * r, 0u);
-                        v[r].x += w2.x;
-                        v[r].y += w2.y;
-                    }
+                    for (int r = 0; r < NZ; ++r) wn[r] = prc_buf_load_f32(rw, vo4, 1024u * r);
                 }
             };
             // high-occupancy form: nothing is loaded a piece ahead (the other wavefronts of the SIMD cover the latency);
@@ -181,32 +118,19 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
                 float2 u[16], v[16];
                 // zero-padded reference piece: a piece of at most 2048 (3072) samples leaves registers 8..15 (12..15) of
                 // every thread zero -- their loads, window products and first-pass additions are skipped (uniform branch)
-                const int nz = cnt <= 2048 ? 8 : (cnt <= 3072 ? 12 : 16);
-                if (nz == 8) {
-                    issue_u(n0, 8);
+                auto fwd_u = [&](auto nzc) {
+                    constexpr int NZ = decltype(nzc)::value;
+                    issue_u(nzc, n0);
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        u[r] = r < 8 ? (HAS_WIN ? make_float2(un[r].x * wn[r], un[r].y * wn[r]) : un[r]) : make_float2(0.f, 0.f);
-                    issue_v(v, n0, cnt);
+                        u[r] = r < NZ ? (HAS_WIN ? make_float2(un[r].x * wn[r], un[r].y * wn[r]) : un[r]) : make_float2(0.f, 0.f);
+                    caft_load_srv(v, srv, n0 + lb * LB, cnt + LB - 1, N, NV, vo8);
                     __builtin_amdgcn_sched_barrier(0);
-                    ft4096_fwd<0, 8>(u, f);
-                } else if (nz == 12) {
-                    issue_u(n0, 12);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        u[r] = r < 12 ? (HAS_WIN ? make_float2(un[r].x * wn[r], un[r].y * wn[r]) : un[r]) : make_float2(0.f, 0.f);
-                    issue_v(v, n0, cnt);
-                    __builtin_amdgcn_sched_barrier(0);
-                    ft4096_fwd<0, 12>(u, f);
-                } else {
-                    issue_u(n0, 16);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        u[r] = HAS_WIN ? make_float2(un[r].x * wn[r], un[r].y * wn[r]) : un[r];
-                    issue_v(v, n0, cnt);
-                    __builtin_amdgcn_sched_barrier(0);
-                    ft4096_fwd<0, 16>(u, f);
-                }
+                    ft4096_fwd<0, NZ>(u, f);
+                };
+                if (cnt <= 2048) fwd_u(caft_int<8>());
+                else if (cnt <= 3072) fwd_u(caft_int<12>());
+                else fwd_u(caft_int<16>());
                 __builtin_amdgcn_sched_barrier(0);
                 ft4096_fwd<1>(v, f);
 #pragma unroll
@@ -217,12 +141,7 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
             const int L0 = lb * LB;
             __builtin_amdgcn_sched_barrier(0);
             if (tail > 0) caft_tail<HAS_WIN>(acc, ref, srv, win, hi_f, tail, L0, LB, R, N, NV, t);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int within = 256 * r + t;
-                const int lag = L0 + within;
-                if (within < LB && lag <= R) ych[caf_y_off(a.s, b, j, R - lag)] = make_float2(acc[r].x * sc, -acc[r].y * sc);
-            }
+            caft_store(acc, a.s, ych, b, j, L0, LB, R, t);
         }
     }
 }
@@ -235,11 +154,7 @@ double caf_team_blocking(int64_t q1, int range_bins, int* nlb_out, int* lb_out) 
     for (int nlb = 1; nlb <= 64; ++nlb) {
         const int lb = (range_bins + nlb) / nlb;               // ceil((R+1)/nlb)
         if (lb > 3073) continue;
-        const int64_t Bp = FT_P + 1 - lb;
-        int64_t pieces = q1 / Bp;
-        const int64_t rest = q1 % Bp;
-        if (rest > CAFT_TAIL_MAX || pieces == 0) ++pieces;
-        const double cost = (double)nlb * (2.0 * (double)pieces + 1.0);
+        const double cost = (double)nlb * (2.0 * (double)caft_pieces(q1, lb) + 1.0);
         if (cost < best) { best = cost; best_nlb = nlb; best_lb = lb; }
         if (lb <= 2) break;
     }

@@ -8,62 +8,18 @@
 // for this kernel to be BUILT and measured against the four-wavefront one; selected by PRC_OPT_CAF_TEAM8).
 #include "caf_internal.h"
 #include "fft_team8.h"
-#include "caf_team_tail.h"
+#include "caf_team.h"
 
 #ifndef CAF8_WAVES_PER_SIMD
 #define CAF8_WAVES_PER_SIMD 6            // three 512-thread teams per CU
 #endif
 
-// Direct lag products of the `tail` samples after the last full piece, time layout of fft_team8.h (lag 512 r + t)
-template <bool HAS_WIN>
-__device__ __forceinline__ void caf8_tail(float2 (&acc)[8], const float2* __restrict__ ref, const float2* __restrict__ srv,
-                                          const float* __restrict__ win, int hi_f, int tail, int L0, int LB, int R, int N,
-                                          int NV, int t) {
-    const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv, (unsigned)NV * 8u);
-    for (int i = 0; i < tail; ++i) {
-        const int n1 = hi_f + 1 + i;
-        float2 uu = make_float2(0.f, 0.f);
-        if (n1 < NV) {
-            uu = ref[n1];
-            if (HAS_WIN) { const float w = win[n1]; uu.x *= w; uu.y *= w; }
-        }
-        uu.x *= (float)F8_P;
-        uu.y *= (float)F8_P;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int within = 512 * r + t;
-            const int lag = L0 + within;
-            int idx = n1 + lag;
-            if (idx >= N) idx -= N;
-            const bool ok = within < LB && lag <= R;
-            const float2 sv = prc_buf_load_c64(rs, ok ? (unsigned)idx * 8u : 0xFFFFFFF0u, 0u);
-            cmac_conj_a(acc[r], uu, sv);
-        }
-    }
-}
-
 template <bool HAS_WIN>
 __global__ __launch_bounds__(F8_THREADS, CAF8_WAVES_PER_SIMD) void caf_fft_team8_kernel(CafTeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* lds = reinterpret_cast<float2*>(smem_raw);
-    // workgroup -> (channel, frame, chunk of segments): exactly caf_fft_team_kernel's mapping (co-located channels and
-    // overlapping frames per XCD)
-    const int per_xcd = (a.nchunks + 7) >> 3;
-    const int slot = (int)(blockIdx.x >> 3);
-    const int ch = slot % a.nref, ci = slot / a.nref;
-    int b, bx;
-    if (a.pair_half > 0) {
-        const int k = ci & 1, A = (ci >> 1) * 8 + (int)(blockIdx.x & 7u);
-        if (A >= (a.nframes + 1) * a.pair_half) return;         // uniform, before any barrier
-        b = A / a.pair_half - k;
-        bx = A % a.pair_half + k * a.pair_half;
-        if (b < 0 || b >= a.nframes || bx >= a.chunks_x) return;
-    } else {
-        const int chunk = a.xcd_contig ? (int)(blockIdx.x & 7u) * per_xcd + ci : ci * 8 + (int)(blockIdx.x & 7u);
-        if (ci >= per_xcd || chunk >= a.nchunks) return;        // uniform, before any barrier
-        b = chunk / a.chunks_x;
-        bx = chunk - b * a.chunks_x;
-    }
+    int ch, b, bx;
+    if (!caft_work(a, &ch, &b, &bx)) return;
     const float2* __restrict__ ref = a.refs[ch] + (int64_t)b * a.s.frame_stride;
     const float2* __restrict__ srv = a.s.srv + (int64_t)b * a.s.frame_stride;
     const float* __restrict__ win = a.s.window;
@@ -75,20 +31,12 @@ __global__ __launch_bounds__(F8_THREADS, CAF8_WAVES_PER_SIMD) void caf_fft_team8
     const int R = a.s.range_bins;
     const int B = a.piece, LB = a.lagblk;
     const unsigned vo8 = (unsigned)t * 8u, vo4 = (unsigned)t * 4u;
-    auto clampu = [](int x) { return x < 0 ? 0u : (unsigned)x; };
-    const float sc = 1.0f / (float)F8_P;
 
     for (int sg = 0; sg < a.segs; ++sg) {
         const int64_t j = (int64_t)bx * a.segs + sg;
         if (j >= a.s.freq_bins) break;                         // uniform
-        const int64_t n_hi64 = j * a.s.q + a.s.half;
-        const int64_t n_lo64 = n_hi64 - (a.s.ntaps - 1);
-        const int lo = n_lo64 < 0 ? 0 : (int)n_lo64;
-        const int hi = n_hi64 > N - 1 ? N - 1 : (int)n_hi64;
-        const int len = hi - lo + 1;
-        int tail = len % B;                                    // a short remainder after the last full piece goes the direct way
-        if (tail > CAFT_TAIL_MAX || len < B) tail = 0;
-        const int hi_f = hi - tail;                            // last sample that goes through the transforms
+        const CaftSeg seg = caft_segment(a.s, j, N, B);
+        const int lo = seg.lo, hi_f = seg.hi_f, tail = seg.tail;
 
         for (int lb = 0; lb < a.nlagblk; ++lb) {
             float2 acc[8];
@@ -104,8 +52,8 @@ __global__ __launch_bounds__(F8_THREADS, CAF8_WAVES_PER_SIMD) void caf_fft_team8
                 {
                     int c = cnt;
                     if (NV - n0 < c) c = NV - n0;
-                    const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, clampu(c) * 8u);
-                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + (HAS_WIN ? n0 : 0), HAS_WIN ? clampu(c) * 4u : 0u);
+                    const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, caft_clampu(c) * 8u);
+                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + (HAS_WIN ? n0 : 0), HAS_WIN ? caft_clampu(c) * 4u : 0u);
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
                         if (r < 4 || (r < 6 && nz > 4) || nz > 6) {
@@ -120,30 +68,9 @@ __global__ __launch_bounds__(F8_THREADS, CAF8_WAVES_PER_SIMD) void caf_fft_team8
                         }
                     }
                 }
-                // srv slots [0, cnt + LB - 1) of this lag block: frame offsets start .. with circular wrap (:82); issued
-                // before the reference transform so that they fly under it
-                {
-                    int start = n0 + lb * LB;
-                    if (start >= N) start -= N;
-                    const int want = cnt + LB - 1;
-                    int c1 = want;
-                    if (N - start < c1) c1 = N - start;
-                    if (NV - start < c1) c1 = NV - start;
-                    const __amdgpu_buffer_rsrc_t rv = prc_rsrc(srv + start, clampu(c1) * 8u);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = prc_buf_load_c64(rv, vo8, 4096u * r);
-                    const int over = start + want - N;              // slots that wrapped (uniform, rare)
-                    if (over > 0) {
-                        const __amdgpu_buffer_rsrc_t rw2 = prc_rsrc(srv, clampu(over < NV ? over : NV) * 8u);
-                        const unsigned voff = vo8 - (unsigned)(N - start) * 8u;   // threads before the wrap: out of range
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) {
-                            const float2 w2 = prc_buf_load_c64(rw2, voff + 4096u * r, 0u);
-                            v[r].x += w2.x;
-                            v[r].y += w2.y;
-                        }
-                    }
-                }
+                // surveillance slots [0, cnt + LB - 1) of this lag block, issued before the reference transform so that they
+                // fly under it
+                caft_load_srv(v, srv, n0 + lb * LB, cnt + LB - 1, N, NV, vo8);
                 __builtin_amdgcn_sched_barrier(0);
                 if (nz == 4) f8_fwd<4>(u, f);
                 else if (nz == 6) f8_fwd<6>(u, f);
@@ -156,13 +83,8 @@ __global__ __launch_bounds__(F8_THREADS, CAF8_WAVES_PER_SIMD) void caf_fft_team8
             f8_inv(acc, f);
             const int L0 = lb * LB;
             __builtin_amdgcn_sched_barrier(0);
-            if (tail > 0) caf8_tail<HAS_WIN>(acc, ref, srv, win, hi_f, tail, L0, LB, R, N, NV, t);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int within = 512 * r + t;
-                const int lag = L0 + within;
-                if (within < LB && lag <= R) ych[caf_y_off(a.s, b, j, R - lag)] = make_float2(acc[r].x * sc, -acc[r].y * sc);
-            }
+            if (tail > 0) caft_tail<HAS_WIN>(acc, ref, srv, win, hi_f, tail, L0, LB, R, N, NV, t);
+            caft_store(acc, a.s, ych, b, j, L0, LB, R, t);
         }
     }
 }

@@ -13,8 +13,7 @@
 #endif
 #include "caf_internal.h"
 #include "fft_team.h"
-#include "caf_team_tail.h"
-#include <type_traits>
+#include "caf_team.h"
 
 // ---- several reference channels against ONE surveillance channel (BASELINE config 5: four illuminators) ----------
 // fast_xambg is called once per (reference, surveillance) pair (range_doppler_processing.py:81-86 is the per-pair
@@ -41,8 +40,6 @@ __device__ __forceinline__ float2 cmul_conj_a(float2 u, float2 v) {
     return make_float2(fmaf(u.y, v.y, u.x * v.x), fmaf(-u.y, v.x, u.x * v.y));
 }
 
-template <int N> using caft_int = std::integral_constant<int, N>;
-
 // NZ0 / NZ1: registers per thread that a first / second reference piece can fill (256 NZ >= its samples), fixed per launch
 // by the host from the piece length and the segment length: (8, 8) at config 5, (12, 8) at config 3, (16, 16) otherwise.
 // A shorter piece (first and last segments of a frame) reads zeros beyond its end through the range check.
@@ -59,20 +56,12 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_MULTI_WAVES) void caf_fft_team_mul
     const int R = a.s.range_bins;
     const int B = a.piece, LB = a.lagblk;
     const unsigned vo8 = (unsigned)t * 8u, vo4 = (unsigned)t * 4u;
-    auto clampu = [](int x) { return x < 0 ? 0u : (unsigned)x; };
-    const float sc = 1.0f / (float)FT_P;
 
     for (int sg = 0; sg < a.segs; ++sg) {
         const int64_t j = (int64_t)blockIdx.x * a.segs + sg;
         if (j >= a.s.freq_bins) break;                         // uniform
-        const int64_t n_hi64 = j * a.s.q + a.s.half;
-        const int64_t n_lo64 = n_hi64 - (a.s.ntaps - 1);
-        const int lo = n_lo64 < 0 ? 0 : (int)n_lo64;
-        const int hi = n_hi64 > N - 1 ? N - 1 : (int)n_hi64;
-        const int len = hi - lo + 1;
-        int tail = len % B;
-        if (tail > CAFT_TAIL_MAX || len < B) tail = 0;
-        const int hi_f = hi - tail;
+        const CaftSeg seg = caft_segment(a.s, j, N, B);
+        const int lo = seg.lo, hi_f = seg.hi_f, tail = seg.tail;
         // at most two pieces (checked on the host): [lo, lo + cnt0) and [lo + B, hi_f]
         const int cnt0 = hi_f - lo + 1 < B ? hi_f - lo + 1 : B;
         const int n1p = lo + B;
@@ -80,28 +69,8 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_MULTI_WAVES) void caf_fft_team_mul
         const bool two = cnt1 > 0;
 
         for (int lb = 0; lb < a.nlagblk; ++lb) {
-            auto issue_v = [&](float2 (&v)[16], int n0, int cnt) {
-                int start = n0 + lb * LB;
-                if (start >= N) start -= N;
-                const int want = cnt + LB - 1;
-                int c1 = want;
-                if (N - start < c1) c1 = N - start;
-                if (NV - start < c1) c1 = NV - start;
-                const __amdgpu_buffer_rsrc_t rv = prc_rsrc(srv + start, clampu(c1) * 8u);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = prc_buf_load_c64(rv, vo8, 2048u * r);
-                const int over = start + want - N;
-                if (over > 0) {
-                    const __amdgpu_buffer_rsrc_t rw2 = prc_rsrc(srv, clampu(over < NV ? over : NV) * 8u);
-                    const unsigned voff = vo8 - (unsigned)(N - start) * 8u;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float2 w2 = prc_buf_load_c64(rw2, voff + 2048u * r, 0u);
-                        v[r].x += w2.x;
-                        v[r].y += w2.y;
-                    }
-                }
-            };
+            // surveillance slots [0, cnt + LB - 1) of a piece for this lag block
+            auto issue_v = [&](float2 (&v)[16], int n0, int cnt) { caft_load_srv(v, srv, n0 + lb * LB, cnt + LB - 1, N, NV, vo8); };
             // reference piece one transform ahead: the raw samples and the window land in un / wn; registers beyond the
             // piece (r >= NZ) are not loaded
             constexpr int NZM = NZ0 > NZ1 ? NZ0 : NZ1;
@@ -114,11 +83,11 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_MULTI_WAVES) void caf_fft_team_mul
             auto issue_u = [&](auto nzc, const float2* __restrict__ ref, int n0, int cnt) {
                 constexpr int NZ = decltype(nzc)::value;
                 if (NV - n0 < cnt) cnt = NV - n0;
-                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, clampu(cnt) * 8u);
+                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, caft_clampu(cnt) * 8u);
 #pragma unroll
                 for (int r = 0; r < NZ; ++r) un[r] = prc_buf_load_c64(ru, vo8, 2048u * r);
                 if (HAS_WIN) {
-                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, clampu(cnt) * 4u);
+                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, caft_clampu(cnt) * 4u);
 #pragma unroll
                     for (int r = 0; r < NZ; ++r) wn[r] = prc_buf_load_f32(rw, vo4, 1024u * r);
                 }
@@ -178,12 +147,7 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_MULTI_WAVES) void caf_fft_team_mul
                 ft_team_sync();
                 __builtin_amdgcn_sched_barrier(0);
                 if (tail > 0) caft_tail<HAS_WIN>(acc, ref, srv, win, hi_f, tail, L0, LB, R, N, NV, t);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int within = 256 * r + t;
-                    const int lag = L0 + within;
-                    if (within < LB && lag <= R) ybase[caf_y_off(a.s, b, j, R - lag)] = make_float2(acc[r].x * sc, -acc[r].y * sc);
-                }
+                caft_store(acc, a.s, ybase, b, j, L0, LB, R, t);
             }
         }
     }
@@ -196,10 +160,7 @@ double caf_team_multi_blocking(int64_t q1, int range_bins, int nref, int* nlb_ou
     for (int nlb = 1; nlb <= 64; ++nlb) {
         const int lb = (range_bins + nlb) / nlb;
         if (lb > 3073) continue;
-        const int64_t Bp = FT_P + 1 - lb;
-        int64_t pieces = q1 / Bp;
-        const int64_t rest = q1 % Bp;
-        if (rest > CAFT_TAIL_MAX || pieces == 0) ++pieces;
+        const int64_t pieces = caft_pieces(q1, lb);
         if (pieces <= 2) {
             const double cost = (double)nlb * ((double)pieces + (double)nref * ((double)pieces + 1.0));
             if (best < 0 || cost < best) {
