@@ -100,11 +100,11 @@ __global__ __launch_bounds__(FT_THREADS, CAFT_WAVES_PER_SIMD) void caf_fft_team_
                 const int rem = hi_f - n0 + 1;
                 int cnt = rem < B ? rem : B;
                 if (NV - n0 < cnt) cnt = NV - n0;
-                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, caft_clampu(cnt) * 8u);
+                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
                 for (int r = 0; r < NZ; ++r) un[r] = prc_buf_load_c64(ru, vo8, 2048u * r);
                 if (HAS_WIN) {
-                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, caft_clampu(cnt) * 4u);
+                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + n0, prc_clampu(cnt) * 4u);
 #pragma unroll
                     for (int r = 0; r < NZ; ++r) wn[r] = prc_buf_load_f32(rw, vo4, 1024u * r);
                 }

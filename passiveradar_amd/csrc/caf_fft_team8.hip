@@ -52,8 +52,8 @@ __global__ __launch_bounds__(F8_THREADS, CAF8_WAVES_PER_SIMD) void caf_fft_team8
                 {
                     int c = cnt;
                     if (NV - n0 < c) c = NV - n0;
-                    const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, caft_clampu(c) * 8u);
-                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + (HAS_WIN ? n0 : 0), HAS_WIN ? caft_clampu(c) * 4u : 0u);
+                    const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + n0, prc_clampu(c) * 8u);
+                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(win + (HAS_WIN ? n0 : 0), HAS_WIN ? prc_clampu(c) * 4u : 0u);
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
                         if (r < 4 || (r < 6 && nz > 4) || nz > 6) {

@@ -41,8 +41,6 @@ static inline int64_t caft_pieces(int64_t q1, int lb) {
 
 template <int N> using caft_int = std::integral_constant<int, N>;
 
-__device__ __forceinline__ unsigned caft_clampu(int x) { return x < 0 ? 0u : (unsigned)x; }
-
 // Workgroup -> (channel ch, frame b, chunk of segments bx); false: this workgroup has no work (uniform, before any barrier).
 // Workgroups reach the eight XCDs round-robin in launch order and every XCD has its own L2: workgroup
 // L (XCD L & 7, slot L >> 3 there) takes channel (L >> 3) % nref of chunk 8 ((L >> 3) / nref) + (L & 7).  The channels of
@@ -102,12 +100,12 @@ __device__ __forceinline__ void caft_load_srv(float2 (&v)[NR], const float2* __r
     int c1 = want;
     if (N - start < c1) c1 = N - start;
     if (NV - start < c1) c1 = NV - start;
-    const __amdgpu_buffer_rsrc_t rv = prc_rsrc(srv + start, caft_clampu(c1) * 8u);
+    const __amdgpu_buffer_rsrc_t rv = prc_rsrc(srv + start, prc_clampu(c1) * 8u);
 #pragma unroll
     for (int r = 0; r < NR; ++r) v[r] = prc_buf_load_c64(rv, vo8, STEP * r);
     const int over = start + want - N;                          // slots that wrapped (uniform, rare)
     if (over > 0) {
-        const __amdgpu_buffer_rsrc_t rw2 = prc_rsrc(srv, caft_clampu(over < NV ? over : NV) * 8u);
+        const __amdgpu_buffer_rsrc_t rw2 = prc_rsrc(srv, prc_clampu(over < NV ? over : NV) * 8u);
         const unsigned voff = vo8 - (unsigned)(N - start) * 8u; // threads before the wrap: out of range
 #pragma unroll
         for (int r = 0; r < NR; ++r) {

@@ -134,6 +134,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t prc_rsrc(const void* base, uns
     void* q = (void*)(((unsigned long long)hi << 32) | lo);
     return __builtin_amdgcn_make_buffer_rsrc(q, (short)0, (int)nb, 0x00020000);
 }
+// byte counts of a descriptor come from differences that may go negative (a piece past the end): those read nothing
+__device__ __forceinline__ unsigned prc_clampu(int x) { return x < 0 ? 0u : (unsigned)x; }
 __device__ __forceinline__ float2 prc_buf_load_c64(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     const prc_v2u x = __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0);
     return make_float2(__uint_as_float(x.x), __uint_as_float(x.y));

@@ -14,58 +14,40 @@
 // step e^{j theta 64 r}; the <= peek samples that wrapped around the block end (np.roll at :139)
 // restart the ramp at index 0 and take their own phase theta*index (Taylor for small arguments).  All loads are branch-free (clamped address + select) and issued one FFT ahead of
 // their use, so each loop body is a single straight-line block the scheduler can overlap.
-#include "ls_internal.h"
+#include "ls_pieces.h"
 #include "fft_wave.h"
 
 int fftw_device_tables(const float2** out);   // caf_fft.hip
 
 #define LSF_WAVES 4
 
-// exp(j x): 7th-order Taylor for |x| <= 0.3 (error < 2e-9, the usual case: Doppler bins of a few Hz), sincosf
-// beyond (bins of kHz at a few hundred kHz of sample rate; only ever reached in the rarely taken wrap branches)
-__device__ __forceinline__ float2 small_rot(float x) {
-    if (fabsf(x) > 0.3f) {
-        float s, c;
-        sincosf(x, &s, &c);
-        return make_float2(c, s);
-    }
-    const float x2 = x * x;
-    const float c = 1.f + x2 * (-0.5f + x2 * (1.f / 24.f + x2 * (-1.f / 720.f)));
-    const float s = x * (1.f + x2 * (-1.f / 6.f + x2 * (1.f / 120.f + x2 * (-1.f / 5040.f))));
-    return make_float2(c, s);
-}
-// index of a wrapped sample inside [0, peek]: lanes outside the wrapped run carry zeros, keep their phase argument small
-__device__ __forceinline__ float wrap_index(int k, int peek) { return (float)(k < 0 ? 0 : (k > peek ? peek : k)); }
-
-struct RefSlot {       // one register slot of the rotated reference, before the data arrived
-    bool ok;           // slot carries a sample (else zero)
-    bool wr;           // source index wrapped around the block end
-    int off;           // clamped source offset into ref
+// What every kernel of this file starts with, after the twiddle tables landed in LDS at `tab` (dynamic LDS: tables, one tile
+// per wave, then what the kernel parks behind them): the lane's constants, the wave's place in the grid and the block's
+// streams.  The table load itself stays in the kernels: blockDim.x read two inlining levels down is no longer folded into
+// one scalar load, and pointers the kernel derives from `tab` must come from its own copy (else: more LDS instructions).
+struct LsWaveCtx {
+    float2* tile;                    // this wave's exchange tile, behind the tables
+    FftLane f;
+    int wave_id, wg, nwaves, b;      // wave in the workgroup / in the block's grid row, waves per row, block
+    const float2* ref;
+    const float2* srv;
+    int n, T, B, ext;                // samples per block, taps, samples per piece, history slots T - 1
 };
-
-// logical r[m] = ref[(m+peek) mod n] * exp(j phi((m+peek) mod n)),  m may lie outside [0, n)
-__device__ __forceinline__ RefSlot ref_slot(int m, int n, int peek, bool circular, bool want) {
-    RefSlot s;
-    s.wr = false;
-    bool ok = want;
-    if (m >= n) { if (circular) { m -= n; s.wr = true; } else ok = false; }
-    if (m < 0) { if (circular) { m += n; s.wr = true; } else ok = false; }
-    int off = m + peek;
-    if (off >= n) { off -= n; s.wr = true; }
-    s.ok = ok;
-    s.off = ok ? off : 0;
-    return s;
-}
-
-__device__ __forceinline__ float2 ref_finish(float2 raw, const RefSlot& s, int rot, float theta32,
-                                             float2 base, float2 step) {
-    float2 v = raw;
-    if (rot) {
-        const float2 cont = cmul(base, step);
-        const float2 wrapped = small_rot(theta32 * (float)(s.wr ? s.off : 0));
-        v = cmul(v, s.wr ? wrapped : cont);
-    }
-    return s.ok ? v : make_float2(0.f, 0.f);
+__device__ __forceinline__ LsWaveCtx ls_wave_setup(const LsFftArgs& a, float2* tab) {
+    LsWaveCtx c;
+    c.tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
+    c.f = fft_lane_setup();
+    c.wave_id = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    c.wg = blockIdx.x * LSF_WAVES + c.wave_id;
+    c.nwaves = gridDim.x * LSF_WAVES;
+    c.b = blockIdx.y;
+    c.ref = a.ref + (int64_t)c.b * a.ref_stride;
+    c.srv = a.srv + (int64_t)c.b * a.srv_stride;
+    c.n = (int)a.n;
+    c.T = a.T;
+    c.B = a.piece;
+    c.ext = a.T - 1;
+    return c;
 }
 
 // AUTO: also accumulate the reference autocorrelation (3 FFTs per piece); otherwise only the
@@ -74,18 +56,11 @@ template <bool AUTO>
 __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_kernel(LsFftArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* tab = reinterpret_cast<float2*>(smem_raw);
-    float2* tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
     fft_load_tables(tab, a.tab);
     __syncthreads();
-    const FftLane f = fft_lane_setup();
-    const int lane = f.lane;
-    const int wg = blockIdx.x * LSF_WAVES + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * LSF_WAVES;
-    const int b = blockIdx.y;
-    const float2* __restrict__ ref = a.ref + (int64_t)b * a.ref_stride;
-    const float2* __restrict__ srv = a.srv + (int64_t)b * a.srv_stride;
-    const int n = (int)a.n;
-    const int T = a.T, B = a.piece, ext = T - 1;
+    const LsWaveCtx c = ls_wave_setup(a, tab);
+    const float2 *__restrict__ ref = c.ref, *__restrict__ srv = c.srv;
+    const int lane = c.f.lane, wg = c.wg, nwaves = c.nwaves, b = c.b, n = c.n, T = c.T, B = c.B, ext = c.ext;
     const bool circ = a.circular != 0;
 
     float2 wrr[16], wrs[16];
@@ -95,7 +70,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_kern
     const int npieces = (n + B - 1) / B;
     // pipeline state: raw reference slots of the NEXT piece to process
     float2 en[16];
-    RefSlot es[16];
+    LsSlot es[16];
     float2 ebase = make_float2(1.f, 0.f);
     int ecnt = 0;
     auto issue_e = [&](int p) {
@@ -107,7 +82,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_kern
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int idx = 64 * r + lane;
-            es[r] = ref_slot(m0 + idx, n, a.peek, circ, idx < ecnt + ext);
+            es[r] = ls_slot(m0 + idx, n, a.peek, circ, idx < ecnt + ext);
             en[r] = ref[es[r].off];
         }
     };
@@ -118,11 +93,11 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_kern
         float2 u[16], v[16], sv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            v[r] = ref_finish(en[r], es[r], a.rot, a.theta32, ebase, a.step[r]);
+            v[r] = ls_slot_finish(en[r], es[r], a.rot, a.theta32, ebase, a.step[r]);
             u[r] = (64 * r + lane) < cnt ? v[r] : make_float2(0.f, 0.f);
         }
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_fwd(u, tile, tab, f);
+        fft1024_fwd(u, c.tile, tab, c.f);
         __builtin_amdgcn_sched_barrier(0);
         // issue the surveillance slots of this piece (consumed one or two FFTs later)
 #pragma unroll
@@ -135,7 +110,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_kern
         }
         __builtin_amdgcn_sched_barrier(0);
         if (AUTO) {
-            fft1024_fwd(v, tile, tab, f);
+            fft1024_fwd(v, c.tile, tab, c.f);
 #pragma unroll
             for (int m = 0; m < 16; ++m) cmac_conj_a(wrr[m], u[m], v[m]);
         }
@@ -148,60 +123,40 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_kern
             const bool ok = idx < cnt + ext && (circ || m0 + idx < n);
             v[r] = ok ? sv[r] : make_float2(0.f, 0.f);
         }
-        fft1024_fwd(v, tile, tab, f);
+        fft1024_fwd(v, c.tile, tab, c.f);
 #pragma unroll
         for (int m = 0; m < 16; ++m) cmac_conj_a(wrs[m], u[m], v[m]);
     }
-    if (AUTO) fft1024_inv(wrr, tile, tab, f);
-    fft1024_inv(wrs, tile, tab, f);
+    if (AUTO) fft1024_inv(wrr, c.tile, tab, c.f);
+    fft1024_inv(wrs, c.tile, tab, c.f);
     // partial[b][wave][0/1][lag] holds conj(g) so that the Levinson prologue's conj() restores g
     float2* __restrict__ part = a.partial + ((int64_t)b * nwaves + wg) * 2 * T;
-    const float sc = 1.0f / 1024.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lag = 64 * r + lane;
-        if (lag < T) {
-            if (AUTO) part[lag] = make_float2(wrr[r].x * sc, -wrr[r].y * sc);
-            part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
-    }
+    ls_store_partial<64, AUTO>(part, wrr, wrs, T, lane, 1.0f / 1024.0f);
 }
 
 __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_kernel(LsFftArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* tab = reinterpret_cast<float2*>(smem_raw);
-    float2* tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
     fft_load_tables(tab, a.tab);
     __syncthreads();
-    const FftLane f = fft_lane_setup();
-    const int lane = f.lane;
-    const int wg = blockIdx.x * LSF_WAVES + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * LSF_WAVES;
-    const int b = blockIdx.y;
-    const float2* __restrict__ ref = a.ref + (int64_t)b * a.ref_stride;
-    const float2* __restrict__ srv = a.srv + (int64_t)b * a.srv_stride;
+    const LsWaveCtx c = ls_wave_setup(a, tab);
+    const float2 *__restrict__ ref = c.ref, *__restrict__ srv = c.srv;
+    const int lane = c.f.lane, wg = c.wg, nwaves = c.nwaves, b = c.b, n = c.n, T = c.T, B = c.B, ext = c.ext;
     float2* __restrict__ out = a.out + (int64_t)b * a.out_stride;
     const double2* __restrict__ taps = a.taps + (int64_t)b * a.T;
-    const int n = (int)a.n;
-    const int T = a.T, B = a.piece, ext = T - 1;
     const bool circ = a.circular != 0;
 
     // H = FFT(taps zero padded) / 1024, once per wave
     float2 h[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int idx = 64 * r + lane;
-        const double2 t = taps[idx < T ? idx : 0];
-        h[r] = idx < T ? make_float2((float)t.x, (float)t.y) : make_float2(0.f, 0.f);
-    }
-    fft1024_fwd(h, tile, tab, f);
-    const float sc = f.sg * (1.0f / 1024.0f);        // 1/1024 and the inverse FFT's quad sign (PRESCALED)
+    ls_load_taps<64>(h, taps, T, lane);
+    fft1024_fwd(h, c.tile, tab, c.f);
+    const float sc = c.f.sg * (1.0f / 1024.0f);        // 1/1024 and the inverse FFT's quad sign (PRESCALED)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { h[r].x *= sc; h[r].y *= sc; }
 
     const int nblocks = (n + B - 1) / B;
     float2 xn[16];
-    RefSlot xs[16];
+    LsSlot xs[16];
     float2 xbase = make_float2(1.f, 0.f);
     auto issue_x = [&](int p) {
         const bool live = p < nblocks;
@@ -210,7 +165,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_kernel(LsFftArgs
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = mstart + 64 * r + lane;
-            xs[r] = ref_slot(m, n, a.peek, circ, live && m < n);
+            xs[r] = ls_slot(m, n, a.peek, circ, live && m < n);
             xn[r] = ref[xs[r].off];
         }
     };
@@ -224,15 +179,15 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_kernel(LsFftArgs
             sv[r] = srv[(nn >= 0 && nn < n) ? nn : 0];
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) x[r] = ref_finish(xn[r], xs[r], a.rot, a.theta32, xbase, a.step[r]);
+        for (int r = 0; r < 16; ++r) x[r] = ls_slot_finish(xn[r], xs[r], a.rot, a.theta32, xbase, a.step[r]);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_fwd(x, tile, tab, f);
+        fft1024_fwd(x, c.tile, tab, c.f);
 #pragma unroll
         for (int r = 0; r < 16; ++r) x[r] = cmul(x[r], h[r]);
         __builtin_amdgcn_sched_barrier(0);
         issue_x(p + nwaves);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_inv<true>(x, tile, tab, f);
+        fft1024_inv<true>(x, c.tile, tab, c.f);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int idx = 64 * r + lane;
@@ -249,25 +204,17 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_kernel(LsFftArgs
 // the prefetch past the last piece), so the loop bodies carry no per-lane compares, selects or
 // 64-bit address arithmetic.  The <= peek samples whose source index wrapped around the block end
 // (np.roll at :139) are patched in by a wave-uniform, rarely taken branch with their own phase.
-__device__ __forceinline__ unsigned lsf_clampu(int x) { return x < 0 ? 0u : (unsigned)x; }
 
 template <bool AUTO>
 __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_lin_kernel(LsFftArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* tab = reinterpret_cast<float2*>(smem_raw);
-    float2* tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
     fft_load_tables(tab, a.tab);
     __syncthreads();
-    const FftLane f = fft_lane_setup();
-    const int lane = f.lane;
-    const int wave_id = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wg = blockIdx.x * LSF_WAVES + wave_id;
-    const int nwaves = gridDim.x * LSF_WAVES;
-    const int b = blockIdx.y;
-    const float2* __restrict__ ref = a.ref + (int64_t)b * a.ref_stride;
-    const float2* __restrict__ srv = a.srv + (int64_t)b * a.srv_stride;
-    const int n = (int)a.n;
-    const int T = a.T, B = a.piece, ext = T - 1, peek = a.peek;
+    const LsWaveCtx c = ls_wave_setup(a, tab);
+    const float2 *__restrict__ ref = c.ref, *__restrict__ srv = c.srv;
+    const int lane = c.f.lane, wg = c.wg, nwaves = c.nwaves, b = c.b, n = c.n, T = c.T, B = c.B, ext = c.ext;
+    const int peek = a.peek;
     const unsigned vo8 = (unsigned)lane * 8u;
 
     float2 wrr[16], wrs[16];
@@ -284,7 +231,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_lin_
         const int cnt = live ? (rem < B ? rem : B) : 0;
         int ce = live ? cnt + ext : 0;                        // slots wanted
         if (n - peek - m0 < ce) ce = n - peek - m0;           // ... whose source m+peek does not wrap
-        const __amdgpu_buffer_rsrc_t re = prc_rsrc(ref + m0 + peek, lsf_clampu(ce) * 8u);
+        const __amdgpu_buffer_rsrc_t re = prc_rsrc(ref + m0 + peek, prc_clampu(ce) * 8u);
         if (a.rot) ebase = phase_rot(a.pr, (int64_t)m0 + lane + peek);
 #pragma unroll
         for (int r = 0; r < 16; ++r) en[r] = prc_buf_load_c64(re, vo8, 512u * r);
@@ -301,83 +248,53 @@ __global__ __launch_bounds__(64 * LSF_WAVES, AUTO ? 1 : 2) void ls_corr_fft_lin_
         const int wstart = n - peek - m0;                     // first wrapped slot of this piece
         int want = cnt + ext;
         if (n - m0 < want) want = n - m0;                     // linear correlation: nothing beyond the block
-        if (peek > 0 && want > wstart) {
-            const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref, lsf_clampu(want - wstart) * 8u);
-            const unsigned voff = vo8 - (unsigned)wstart * 8u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float2 w = prc_buf_load_c64(rw, voff + 512u * r, 0u);
-                if (a.rot) w = cmul(w, small_rot(a.theta32 * wrap_index(64 * r + lane - wstart, peek)));
-                v[r].x += w.x;
-                v[r].y += w.y;
-            }
-        }
+        ls_add_wrapped_tail<64, true>(v, ref, vo8, wstart, peek, want, lane, a.rot, a.theta32);
 #pragma unroll
         for (int r = 0; r < 16; ++r) u[r] = (64 * r + lane) < cnt ? v[r] : make_float2(0.f, 0.f);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_fwd(u, tile, tab, f);
+        fft1024_fwd(u, c.tile, tab, c.f);
         __builtin_amdgcn_sched_barrier(0);
         {   // surveillance slots of this piece (consumed one or two FFTs later)
-            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + m0, lsf_clampu(want) * 8u);
+            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + m0, prc_clampu(want) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) sv[r] = prc_buf_load_c64(rs, vo8, 512u * r);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (AUTO) {
-            fft1024_fwd(v, tile, tab, f);
+            fft1024_fwd(v, c.tile, tab, c.f);
 #pragma unroll
             for (int m = 0; m < 16; ++m) cmac_conj_a(wrr[m], u[m], v[m]);
         }
         __builtin_amdgcn_sched_barrier(0);
         issue_e(p + nwaves);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_fwd(sv, tile, tab, f);
+        fft1024_fwd(sv, c.tile, tab, c.f);
 #pragma unroll
         for (int m = 0; m < 16; ++m) cmac_conj_a(wrs[m], u[m], sv[m]);
     }
-    if (AUTO) fft1024_inv(wrr, tile, tab, f);
-    fft1024_inv(wrs, tile, tab, f);
+    if (AUTO) fft1024_inv(wrr, c.tile, tab, c.f);
+    fft1024_inv(wrs, c.tile, tab, c.f);
     float2* __restrict__ part = a.partial + ((int64_t)b * nwaves + wg) * 2 * T;
-    const float sc = 1.0f / 1024.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lag = 64 * r + lane;
-        if (lag < T) {
-            if (AUTO) part[lag] = make_float2(wrr[r].x * sc, -wrr[r].y * sc);
-            part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
-    }
+    ls_store_partial<64, AUTO>(part, wrr, wrs, T, lane, 1.0f / 1024.0f);
 }
 
 __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_lin_kernel(LsFftArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* tab = reinterpret_cast<float2*>(smem_raw);
-    float2* tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
     fft_load_tables(tab, a.tab);
     __syncthreads();
-    const FftLane f = fft_lane_setup();
-    const int lane = f.lane;
-    const int wave_id = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wg = blockIdx.x * LSF_WAVES + wave_id;
-    const int nwaves = gridDim.x * LSF_WAVES;
-    const int b = blockIdx.y;
-    const float2* __restrict__ ref = a.ref + (int64_t)b * a.ref_stride;
-    const float2* __restrict__ srv = a.srv + (int64_t)b * a.srv_stride;
+    const LsWaveCtx c = ls_wave_setup(a, tab);
+    const float2 *__restrict__ ref = c.ref, *__restrict__ srv = c.srv;
+    const int lane = c.f.lane, wg = c.wg, nwaves = c.nwaves, b = c.b, n = c.n, T = c.T, B = c.B, ext = c.ext;
     float2* __restrict__ out = a.out + (int64_t)b * a.out_stride;
     const double2* __restrict__ taps = a.taps + (int64_t)b * a.T;
-    const int n = (int)a.n;
-    const int T = a.T, B = a.piece, ext = T - 1, peek = a.peek;
+    const int peek = a.peek;
     const unsigned vo8 = (unsigned)lane * 8u;
 
     float2 h[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int idx = 64 * r + lane;
-        const double2 t = taps[idx < T ? idx : 0];
-        h[r] = idx < T ? make_float2((float)t.x, (float)t.y) : make_float2(0.f, 0.f);
-    }
-    fft1024_fwd(h, tile, tab, f);
-    const float sc = f.sg * (1.0f / 1024.0f);        // 1/1024 and the inverse FFT's quad sign (PRESCALED)
+    ls_load_taps<64>(h, taps, T, lane);
+    fft1024_fwd(h, c.tile, tab, c.f);
+    const float sc = c.f.sg * (1.0f / 1024.0f);        // 1/1024 and the inverse FFT's quad sign (PRESCALED)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { h[r].x *= sc; h[r].y *= sc; }
 
@@ -385,7 +302,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_lin_kernel(LsFft
     // unwrapped reference: slot idx of block p <-> ref[peek + mstart + idx], valid for 0 <= mstart+idx < n-peek:
     // one descriptor for the whole block (base ref+peek), the lane offset carries mstart (negative
     // for the first block: wraps to a huge unsigned offset -> out of range -> 0)
-    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, lsf_clampu(n - peek) * 8u);
+    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, prc_clampu(n - peek) * 8u);
     float2 xn[16];
     float2 xbase = make_float2(1.f, 0.f);
     auto issue_x = [&](int p) {
@@ -403,22 +320,10 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_lin_kernel(LsFft
         float2 x[16], sv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) x[r] = a.rot ? cmul(xn[r], cmul(xbase, a.step[r])) : xn[r];
-        const int wstart = n - peek - mstart;                 // first slot whose source wrapped (rare)
-        if (peek > 0 && wstart < FFTW_P) {
-            int cw = FFTW_P - wstart;
-            if (cw > peek) cw = peek;
-            const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref, lsf_clampu(cw) * 8u);
-            const unsigned voff = vo8 - (unsigned)wstart * 8u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float2 w = prc_buf_load_c64(rw, voff + 512u * r, 0u);
-                if (a.rot) w = cmul(w, small_rot(a.theta32 * wrap_index(64 * r + lane - wstart, peek)));
-                x[r].x += w.x;
-                x[r].y += w.y;
-            }
-        }
+        // first slot whose source wrapped: n - peek - mstart (rare)
+        ls_add_wrapped_tail<64, true>(x, ref, vo8, n - peek - mstart, peek, FFTW_P, lane, a.rot, a.theta32);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_fwd(x, tile, tab, f);
+        fft1024_fwd(x, c.tile, tab, c.f);
 #pragma unroll
         for (int r = 0; r < 16; ++r) x[r] = cmul(x[r], h[r]);
         __builtin_amdgcn_sched_barrier(0);
@@ -427,13 +332,13 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_lin_kernel(LsFft
         const int cnt = (n - n0) < B ? (n - n0) : B;
         const unsigned vout = vo8 - (unsigned)ext * 8u;
         {
-            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, lsf_clampu(cnt) * 8u);
+            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) sv[r] = prc_buf_load_c64(rs, vout + 512u * r, 0u);
         }
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_inv<true>(x, tile, tab, f);
-        const __amdgpu_buffer_rsrc_t ro = prc_rsrc(out + n0, lsf_clampu(cnt) * 8u);
+        fft1024_inv<true>(x, c.tile, tab, c.f);
+        const __amdgpu_buffer_rsrc_t ro = prc_rsrc(out + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             prc_v2u d;
@@ -455,57 +360,34 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fir_fft_lin_kernel(LsFft
 // zeros elsewhere,  sum_n s[n] conj(rho[n-k]) = IFFT( FFT(s slots) conj(X_p) )[k]  for k <= ext.
 // The <= peek samples whose source wrapped (phase ramp restarted, factor gamma) are corrected
 // exactly in the solve kernel (right-hand side) and in ls_edge_fix_kernel (last peek outputs).
-__device__ __forceinline__ void cmac_bconj(float2& w, float2 u, float2 x) {   // w += u * conj(x)
-    w.x = fmaf(u.x, x.x, w.x);
-    w.x = fmaf(u.y, x.y, w.x);
-    w.y = fmaf(u.y, x.x, w.y);
-    w.y = fmaf(-u.x, x.y, w.y);
-}
-
 __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_corr_cached_kernel(LsFftArgs a) {
-    constexpr bool FIRST = true;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* tab = reinterpret_cast<float2*>(smem_raw);
-    float2* tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
     fft_load_tables(tab, a.tab);
     __syncthreads();
-    const FftLane f = fft_lane_setup();
-    const int lane = f.lane;
-    const int wave_id = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wg = blockIdx.x * LSF_WAVES + wave_id;
-    const int nwaves = gridDim.x * LSF_WAVES;
-    const int b = blockIdx.y;
-    const float2* __restrict__ ref = a.ref + (int64_t)b * a.ref_stride;
-    const float2* __restrict__ srv = a.srv + (int64_t)b * a.srv_stride;
-    const int n = (int)a.n;
-    const int T = a.T, B = a.piece, ext = T - 1, peek = a.peek;
+    const LsWaveCtx c = ls_wave_setup(a, tab);
+    const float2 *__restrict__ ref = c.ref, *__restrict__ srv = c.srv;
+    const int lane = c.f.lane, wg = c.wg, nwaves = c.nwaves, b = c.b, n = c.n, T = c.T, B = c.B, ext = c.ext;
+    const int peek = a.peek;
     const int npieces = (n + B - 1) / B;
     float2* __restrict__ cache = a.cache + (int64_t)b * npieces * FFTW_P;
     const unsigned vo8 = (unsigned)lane * 8u;
     const unsigned vslot = vo8 - (unsigned)ext * 8u;          // slot idx -> piece sample idx-ext (idx<ext: out of range)
-    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, lsf_clampu(n - peek) * 8u);
+    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, prc_clampu(n - peek) * 8u);
 
     // the autocorrelation accumulator lives in LDS (one 8 KB strip per wave, read-modify-write once per piece):
     // with it in registers the kernel does not fit two waves per SIMD without scratch spills
-    float2* Wrr = tab + FFTW_TABLE + LSF_WAVES * FFTW_TILE + wave_id * FFTW_P;
+    float2* Wrr = tab + FFTW_TABLE + LSF_WAVES * FFTW_TILE + c.wave_id * FFTW_P;
     float2 wrs[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) { Wrr[64 * m + lane] = make_float2(0.f, 0.f); wrs[m] = make_float2(0.f, 0.f); }
 
     float2 xn[16];                                            // block of the next piece (prefetched)
     auto issue_x = [&](int p) {
-        const bool live = p < npieces;
-        if (FIRST) {
-            const int mstart = (live ? p * B : n) - ext;
-            const unsigned voff = vo8 + (unsigned)mstart * 8u;
+        const int mstart = (p < npieces ? p * B : n) - ext;          // dead prefetch: everything out of range
+        const unsigned voff = vo8 + (unsigned)mstart * 8u;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xn[r] = prc_buf_load_c64(rx, voff + 512u * r, 0u);
-        } else {
-            const __amdgpu_buffer_rsrc_t rc = prc_rsrc(cache + (int64_t)(live ? p : 0) * FFTW_P,
-                                                       live ? FFTW_P * 8u : 0u);
-#pragma unroll
-            for (int m = 0; m < 8; ++m) prc_buf_load_2c64(rc, (unsigned)lane * 16u, 1024u * m, xn[2 * m], xn[2 * m + 1]);
-        }
+        for (int r = 0; r < 16; ++r) xn[r] = prc_buf_load_c64(rx, voff + 512u * r, 0u);
     };
     issue_x(wg);
     for (int p = wg; p < npieces; p += nwaves) {
@@ -517,7 +399,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_corr_cached_kernel(LsFft
         for (int r = 0; r < 16; ++r) x[r] = xn[r];
         // surveillance piece in slots [ext, ext+cnt), rotated by e^{-j theta (n+peek)}
         {
-            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, lsf_clampu(cnt) * 8u);
+            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) u[r] = prc_buf_load_c64(rs, vslot + 512u * r, 0u);
         }
@@ -526,60 +408,25 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_corr_cached_kernel(LsFft
             sbase = phase_rot(a.pr, (int64_t)mstart + lane + peek);
             sbase.y = -sbase.y;
         }
-        if (FIRST) {
-            // wrapped tail of rho (source index restarts at ref[0]); unrotated, so no phase here
-            const int wstart = n - peek - mstart;
-            if (peek > 0 && wstart < FFTW_P) {
-                int cw = FFTW_P - wstart;
-                if (cw > peek) cw = peek;
-                const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref, lsf_clampu(cw) * 8u);
-                const unsigned voff = vo8 - (unsigned)wstart * 8u;
+        // wrapped tail of rho (source index restarts at ref[0]); unrotated, so no phase here
+        ls_add_wrapped_tail<64, false>(x, ref, vo8, n - peek - mstart, peek, FFTW_P);
+        // rho piece in slots [ext, ext+cnt): the same samples, masked by the range check
+        float2 up[16];
+        ls_load_rho_piece<64>(up, ref, n, peek, n0, cnt, vslot);
+        __builtin_amdgcn_sched_barrier(0);
+        fft1024_fwd(x, c.tile, tab, c.f);
+        if (a.cache) {
+            float2* __restrict__ cp = cache + (int64_t)p * FFTW_P;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float2 w = prc_buf_load_c64(rw, voff + 512u * r, 0u);
-                    x[r].x += w.x;
-                    x[r].y += w.y;
-                }
-            }
-            // rho piece in slots [ext, ext+cnt): the same samples, masked by the range check
-            float2 up[16];
-            {
-                int cu = cnt;
-                if (n - peek - n0 < cu) cu = n - peek - n0;
-                const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + peek + n0, lsf_clampu(cu) * 8u);
+            for (int m = 0; m < 8; ++m)
+                reinterpret_cast<float4*>(cp)[64 * m + lane] = make_float4(x[2 * m].x, x[2 * m].y, x[2 * m + 1].x, x[2 * m + 1].y);
+        }
+        fft1024_fwd(up, c.tile, tab, c.f);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) up[r] = prc_buf_load_c64(ru, vslot + 512u * r, 0u);
-                const int wst = n - peek - n0;                // first wrapped sample of the piece
-                if (peek > 0 && wst < cnt) {
-                    // a last piece shorter than peek starts inside the wrapped run (wst < 0): the source then
-                    // starts at ref[-wst], not at ref[0] -- otherwise the slots below `ext` would pick up the
-                    // wrapped samples that belong to the previous piece and count them twice
-                    const int w0 = wst > 0 ? wst : 0;
-                    const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref + (w0 - wst), lsf_clampu(cnt - w0) * 8u);
-                    const unsigned voff = vslot - (unsigned)w0 * 8u;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float2 w = prc_buf_load_c64(rw, voff + 512u * r, 0u);
-                        up[r].x += w.x;
-                        up[r].y += w.y;
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            fft1024_fwd(x, tile, tab, f);
-            if (a.cache) {
-                float2* __restrict__ cp = cache + (int64_t)p * FFTW_P;
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-                    reinterpret_cast<float4*>(cp)[64 * m + lane] = make_float4(x[2 * m].x, x[2 * m].y, x[2 * m + 1].x, x[2 * m + 1].y);
-            }
-            fft1024_fwd(up, tile, tab, f);
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                float2 t = Wrr[64 * m + lane];
-                cmac_bconj(t, up[m], x[m]);
-                Wrr[64 * m + lane] = t;
-            }
+        for (int m = 0; m < 16; ++m) {
+            float2 t = Wrr[64 * m + lane];
+            cmac_conj(t, up[m], x[m]);
+            Wrr[64 * m + lane] = t;
         }
         __builtin_amdgcn_sched_barrier(0);
         if (a.rot) {
@@ -592,26 +439,18 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_corr_cached_kernel(LsFft
         }
         issue_x(p + nwaves);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_fwd(u, tile, tab, f);
+        fft1024_fwd(u, c.tile, tab, c.f);
 #pragma unroll
-        for (int m = 0; m < 16; ++m) cmac_bconj(wrs[m], u[m], x[m]);
+        for (int m = 0; m < 16; ++m) cmac_conj(wrs[m], u[m], x[m]);
     }
-    fft1024_inv(wrs, tile, tab, f);
+    fft1024_inv(wrs, c.tile, tab, c.f);
     float2 wrr[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) wrr[m] = Wrr[64 * m + lane];
-    if (FIRST) fft1024_inv(wrr, tile, tab, f);
+    fft1024_inv(wrr, c.tile, tab, c.f);
     // partial[b][wave][0/1][lag] holds conj(g): the prepare / solve prologues conjugate back
     float2* __restrict__ part = a.partial + ((int64_t)b * nwaves + wg) * 2 * T;
-    const float sc = 1.0f / 1024.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lag = 64 * r + lane;
-        if (lag < T) {
-            if (FIRST) part[lag] = make_float2(wrr[r].x * sc, -wrr[r].y * sc);
-            part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
-    }
+    ls_store_partial<64, true>(part, wrr, wrs, T, lane, 1.0f / 1024.0f);
 }
 
 // FIR of bin i fused with the cross-correlation of bin i+1 (cached-spectrum chain): per block the
@@ -622,28 +461,18 @@ __global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_corr_cached_kernel(LsFft
 // per block).  !CACHED (method 2, or when the cache does not fit): it is recomputed from the reference (6 KB per
 // block + L2-served overlap, one more FFT): fewer HBM bytes but a third transform, which makes the kernel
 // VALU-bound -- measured slower than the HBM-bound cached form.
-#ifndef LSF_FUSED_OCC
-#define LSF_FUSED_OCC 2      // wavefronts per SIMD (A/B builds override it: 3 tells whether more loads in flight help)
-#endif
 template <bool CACHED, bool ROT_IN>
-__global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached_kernel(LsFftArgs a) {
+__global__ __launch_bounds__(64 * LSF_WAVES, 2) void ls_fused_cached_kernel(LsFftArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* tab = reinterpret_cast<float2*>(smem_raw);
-    float2* tile = tab + FFTW_TABLE + (threadIdx.x >> 6) * FFTW_TILE;
     fft_load_tables(tab, a.tab);
     __syncthreads();
-    const FftLane f = fft_lane_setup();
-    const int lane = f.lane;
-    const int wave_id = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wg = blockIdx.x * LSF_WAVES + wave_id;
-    const int nwaves = gridDim.x * LSF_WAVES;
-    const int b = blockIdx.y;
-    const float2* __restrict__ ref = a.ref + (int64_t)b * a.ref_stride;
-    const float2* __restrict__ srv = a.srv + (int64_t)b * a.srv_stride;
+    const LsWaveCtx c = ls_wave_setup(a, tab);
+    const float2 *__restrict__ ref = c.ref, *__restrict__ srv = c.srv;
+    const int lane = c.f.lane, wg = c.wg, nwaves = c.nwaves, b = c.b, n = c.n, T = c.T, B = c.B, ext = c.ext;
     float2* __restrict__ out = a.out + (int64_t)b * a.out_stride;
     const double2* __restrict__ taps = a.taps_t + (int64_t)b * a.T;
-    const int n = (int)a.n;
-    const int T = a.T, B = a.piece, ext = T - 1, peek = a.peek;
+    const int peek = a.peek;
     const int nblocks = (n + B - 1) / B;
     const float2* __restrict__ cache = a.cache + (int64_t)b * nblocks * FFTW_P;
     const unsigned vo8 = (unsigned)lane * 8u;
@@ -653,17 +482,12 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
     // registers costs 32 VGPRs per lane for the whole kernel and pushes the compiler into scratch spills)
     float2* Hs = tab + FFTW_TABLE + LSF_WAVES * FFTW_TILE;
     const float sc = 1.0f / 1024.0f;
-    if (wave_id == 0) {
+    if (c.wave_id == 0) {
         float2 h[16];
+        ls_load_taps<64>(h, taps, T, lane);
+        fft1024_fwd(h, c.tile, tab, c.f);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int idx = 64 * r + lane;
-            const double2 t = taps[idx < T ? idx : 0];
-            h[r] = idx < T ? make_float2((float)t.x, (float)t.y) : make_float2(0.f, 0.f);
-        }
-        fft1024_fwd(h, tile, tab, f);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Hs[64 * r + lane] = make_float2(h[r].x * sc * f.sg, h[r].y * sc * f.sg);   // quad sign of the inverse FFT folded in
+        for (int r = 0; r < 16; ++r) Hs[64 * r + lane] = make_float2(h[r].x * sc * c.f.sg, h[r].y * sc * c.f.sg);   // quad sign of the inverse FFT folded in
     }
     __syncthreads();
 
@@ -671,7 +495,7 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
 #pragma unroll
     for (int m = 0; m < 16; ++m) wrs[m] = make_float2(0.f, 0.f);
 
-    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, lsf_clampu(n - peek) * 8u);
+    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, prc_clampu(n - peek) * 8u);
     float2 xn[16];
     auto issue_x = [&](int p) {
         const bool live = p < nblocks;
@@ -699,64 +523,27 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
         for (int r = 0; r < 16; ++r) xc[r] = xn[r];
         if (!CACHED) {
             // wrapped tail of rho (source index restarts at ref[0]); unrotated, so no phase here
-            const int wstart = n - peek - (n0 - ext);
-            if (peek > 0 && wstart < FFTW_P) {
-                int cw = FFTW_P - wstart;
-                if (cw > peek) cw = peek;
-                const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref, lsf_clampu(cw) * 8u);
-                const unsigned voff = vo8 - (unsigned)wstart * 8u;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float2 w = prc_buf_load_c64(rw, voff + 512u * r, 0u);
-                    xc[r].x += w.x;
-                    xc[r].y += w.y;
-                }
-            }
+            ls_add_wrapped_tail<64, false>(xc, ref, vo8, n - peek - (n0 - ext), peek, FFTW_P);
             __builtin_amdgcn_sched_barrier(0);
-            fft1024_fwd(xc, tile, tab, f);
+            fft1024_fwd(xc, c.tile, tab, c.f);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) y[r] = cmul(xc[r], Hs[64 * r + lane]);
         __builtin_amdgcn_sched_barrier(0);
         issue_x(p + nwaves);
         {
-            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, lsf_clampu(cnt) * 8u);
+            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) sv[r] = prc_buf_load_c64(rs, vslot + 512u * r, 0u);
         }
         // one rotation on the way out: from this bin's frame to the frame of whoever reads the stream next
-        const bool rot_out = a.rot || a.rot2;
-        float2 obase = make_float2(1.f, 0.f), ibase = make_float2(1.f, 0.f);
-        if (rot_out) {
-            const int64_t idx = (int64_t)n0 - ext + lane + peek;
-            const float2 p1 = a.rot ? phase_rot(a.pr, idx) : make_float2(1.f, 0.f);
-            float2 p2 = a.rot2 ? phase_rot(a.pr2, idx) : make_float2(1.f, 0.f);
-            p2.y = -p2.y;
-            obase = cmul(p1, p2);
-            if (ROT_IN) ibase = make_float2(p1.x, -p1.y);
-        }
+        float2 obase, ibase;
+        const bool rot_out = ls_out_rotation<ROT_IN>(a, (int64_t)n0 - ext + lane + peek, obase, ibase);
         __builtin_amdgcn_sched_barrier(0);
-        fft1024_inv<true>(y, tile, tab, f);
+        fft1024_inv<true>(y, c.tile, tab, c.f);
         // last `peek` outputs of the block: rho samples whose ramp restarted carry gamma instead of 1
-        if (a.rot && peek > 0 && n0 + cnt > n - peek) {
-            const float2 g1 = a.gamma_m1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = n0 + 64 * r + lane - ext;
-                const int over = nn - (n - peek);            // 0..peek-1 for affected outputs
-                if (over >= 0 && nn < n) {
-                    float2 acc = make_float2(0.f, 0.f);
-                    for (int k = 0; k <= over && k < T; ++k) {
-                        const double2 wk = taps[k];
-                        cmac(acc, make_float2((float)wk.x, (float)wk.y), ref[over - k]);   // rho[nn-k] = ref[nn-k+peek-n]
-                    }
-                    const float2 c = cmul(g1, acc);
-                    y[r].x += c.x;
-                    y[r].y += c.y;
-                }
-            }
-        }
-        const __amdgpu_buffer_rsrc_t ro = prc_rsrc(out + n0, lsf_clampu(cnt) * 8u);
+        if (a.rot) ls_gamma_edge<64>(y, taps, ref, a.gamma_m1, n, n0, cnt, ext, peek, T, lane);
+        const __amdgpu_buffer_rsrc_t ro = prc_rsrc(out + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float2 sin_ = sv[r];
@@ -778,19 +565,15 @@ __global__ __launch_bounds__(64 * LSF_WAVES, LSF_FUSED_OCC) void ls_fused_cached
             y[r] = in ? o : make_float2(0.f, 0.f);
         }
         if (a.has_next) {
-            fft1024_fwd(y, tile, tab, f);
+            fft1024_fwd(y, c.tile, tab, c.f);
 #pragma unroll
-            for (int m = 0; m < 16; ++m) cmac_bconj(wrs[m], y[m], xc[m]);
+            for (int m = 0; m < 16; ++m) cmac_conj(wrs[m], y[m], xc[m]);
         }
     }
     if (a.has_next) {
-        fft1024_inv(wrs, tile, tab, f);
+        fft1024_inv(wrs, c.tile, tab, c.f);
         float2* __restrict__ part = a.partial + ((int64_t)b * nwaves + wg) * 2 * T;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lag = 64 * r + lane;
-            if (lag < T) part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
+        ls_store_partial<64, false>(part, wrs, wrs, T, lane, sc);
     }
 }
 
@@ -816,85 +599,75 @@ int ls_fft_waves_per_block(int64_t n, int T) {
     return (int)groups * LSF_WAVES;
 }
 
-static void fill_common(LsFftArgs& a, int T, double theta) {
-    a.piece = (int)ls_piece(T);
-    a.theta32 = (float)theta;
-    for (int r = 0; r < 16; ++r) {
-        const double ang = theta * 64.0 * r;
-        a.step[r] = make_float2((float)cos(ang), (float)sin(ang));
-    }
+// what the four launchers share: the piece length, the twiddle tables, a grid of `groups` workgroups per block and the LDS
+// bytes -- tables, one tile per wave and `extra` float2 behind them (the phase steps are the caller's: ls_fill_*)
+struct LsfLaunch {
+    int rc;
+    dim3 grid;
+    size_t lds;
+};
+static LsfLaunch lsf_prepare(LsFftArgs& a, int64_t groups, int nblocks, int extra) {
+    a.piece = (int)ls_piece(a.T);
+    return {fftw_device_tables(&a.tab), dim3((unsigned)groups, (unsigned)nblocks),
+            sizeof(float2) * (FFTW_TABLE + LSF_WAVES * FFTW_TILE + extra)};
 }
 
 int ls_launch_corr_fft(LsFftArgs a, double theta, int waves_per_block, int nblocks, bool with_autocorr,
                        hipStream_t stream) {
-    fill_common(a, a.T, theta);
-    int rc = fftw_device_tables(&a.tab);
-    if (rc) return rc;
-    dim3 grid((unsigned)(waves_per_block / LSF_WAVES), (unsigned)nblocks);
-    const size_t lds = sizeof(float2) * (FFTW_TABLE + LSF_WAVES * FFTW_TILE);
+    ls_fill_steps(a, theta, 64);
+    const LsfLaunch l = lsf_prepare(a, waves_per_block / LSF_WAVES, nblocks, 0);
+    if (l.rc) return l.rc;
     if (!a.circular) {
         if (with_autocorr)
-            hipLaunchKernelGGL(ls_corr_fft_lin_kernel<true>, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+            hipLaunchKernelGGL(ls_corr_fft_lin_kernel<true>, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
         else
-            hipLaunchKernelGGL(ls_corr_fft_lin_kernel<false>, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+            hipLaunchKernelGGL(ls_corr_fft_lin_kernel<false>, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
     } else if (with_autocorr)
-        hipLaunchKernelGGL(ls_corr_fft_kernel<true>, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+        hipLaunchKernelGGL(ls_corr_fft_kernel<true>, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
     else
-        hipLaunchKernelGGL(ls_corr_fft_kernel<false>, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+        hipLaunchKernelGGL(ls_corr_fft_kernel<false>, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
     PRC_LAUNCH_CHECK();
     return PRC_OK;
 }
 
 int ls_launch_fir_fft(LsFftArgs a, double theta, int nblocks, hipStream_t stream) {
-    fill_common(a, a.T, theta);
-    int rc = fftw_device_tables(&a.tab);
-    if (rc) return rc;
-    const int64_t B = a.piece;
+    ls_fill_steps(a, theta, 64);
+    const int64_t B = ls_piece(a.T);
     const int64_t pieces = (a.n + B - 1) / B;
     int64_t groups = (pieces + 16 * LSF_WAVES - 1) / (16 * LSF_WAVES);   // ~16 blocks per wave: the FFT of the taps costs 1/33
     if (groups < 1) groups = 1;
-    dim3 grid((unsigned)groups, (unsigned)nblocks);
-    const size_t lds = sizeof(float2) * (FFTW_TABLE + LSF_WAVES * FFTW_TILE);
+    const LsfLaunch l = lsf_prepare(a, groups, nblocks, 0);
+    if (l.rc) return l.rc;
     if (!a.circular)
-        hipLaunchKernelGGL(ls_fir_fft_lin_kernel, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+        hipLaunchKernelGGL(ls_fir_fft_lin_kernel, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
     else
-        hipLaunchKernelGGL(ls_fir_fft_kernel, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+        hipLaunchKernelGGL(ls_fir_fft_kernel, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
     PRC_LAUNCH_CHECK();
     return PRC_OK;
 }
 
 int ls_launch_corr_cached(LsFftArgs a, double theta, int waves_per_block, int nblocks, hipStream_t stream) {
-    fill_common(a, a.T, theta);
-    int rc = fftw_device_tables(&a.tab);
-    if (rc) return rc;
-    dim3 grid((unsigned)(waves_per_block / LSF_WAVES), (unsigned)nblocks);
-    const size_t lds = sizeof(float2) * (FFTW_TABLE + LSF_WAVES * FFTW_TILE + LSF_WAVES * FFTW_P);
+    ls_fill_steps(a, theta, 64);
+    const LsfLaunch l = lsf_prepare(a, waves_per_block / LSF_WAVES, nblocks, LSF_WAVES * FFTW_P);
+    if (l.rc) return l.rc;
     { int rc_ = prc_lds_optin(reinterpret_cast<const void*>(&ls_corr_cached_kernel), 80 * 1024); if (rc_) return rc_; }
-    hipLaunchKernelGGL(ls_corr_cached_kernel, grid, dim3(64 * LSF_WAVES), lds, stream, a);
+    hipLaunchKernelGGL(ls_corr_cached_kernel, l.grid, dim3(64 * LSF_WAVES), l.lds, stream, a);
     PRC_LAUNCH_CHECK();
     return PRC_OK;
 }
 
 int ls_launch_fused_cached(LsFftArgs a, double theta, double theta_out, double gamma_angle, int waves_per_block,
                            int nblocks, hipStream_t stream) {
-    fill_common(a, a.T, theta);
-    for (int r = 0; r < 16; ++r) {
-        const double ang_in = theta * 64.0 * r, ang = (theta - theta_out) * 64.0 * r;
-        a.step2[r] = make_float2((float)cos(ang_in), (float)sin(ang_in));
-        a.step[r] = make_float2((float)cos(ang), (float)sin(ang));
-    }
-    a.gamma_m1 = make_float2((float)(cos(gamma_angle) - 1.0), (float)sin(gamma_angle));
-    int rc = fftw_device_tables(&a.tab);
-    if (rc) return rc;
-    dim3 grid((unsigned)(waves_per_block / LSF_WAVES), (unsigned)nblocks);
-    const size_t lds = sizeof(float2) * (FFTW_TABLE + LSF_WAVES * FFTW_TILE + FFTW_P);
+    ls_fill_fused(a, theta, theta_out, gamma_angle, 64);
+    const LsfLaunch l = lsf_prepare(a, waves_per_block / LSF_WAVES, nblocks, FFTW_P);
+    if (l.rc) return l.rc;
     const dim3 block(64 * LSF_WAVES);
     if (a.cache) {
-        if (a.rot_in) hipLaunchKernelGGL((ls_fused_cached_kernel<true, true>), grid, block, lds, stream, a);
-        else hipLaunchKernelGGL((ls_fused_cached_kernel<true, false>), grid, block, lds, stream, a);
+        if (a.rot_in) hipLaunchKernelGGL((ls_fused_cached_kernel<true, true>), l.grid, block, l.lds, stream, a);
+        else hipLaunchKernelGGL((ls_fused_cached_kernel<true, false>), l.grid, block, l.lds, stream, a);
     } else {
-        if (a.rot_in) hipLaunchKernelGGL((ls_fused_cached_kernel<false, true>), grid, block, lds, stream, a);
-        else hipLaunchKernelGGL((ls_fused_cached_kernel<false, false>), grid, block, lds, stream, a);
+        if (a.rot_in) hipLaunchKernelGGL((ls_fused_cached_kernel<false, true>), l.grid, block, l.lds, stream, a);
+        else hipLaunchKernelGGL((ls_fused_cached_kernel<false, false>), l.grid, block, l.lds, stream, a);
     }
     PRC_LAUNCH_CHECK();
     return PRC_OK;

@@ -7,53 +7,9 @@
 //   ls_fir_team_kernel  : overlap-save FIR, out = s - IFFT(FFT(r block) FFT(taps))             (:153-155).
 // One workgroup (four wavefronts) per piece; linear (LS_Filter_Toeplitz / _Multiple) and circular (LS_Filter)
 // boundaries; r is the peek-rotated, Doppler-rotated reference generated on the fly as in ls_fft.hip.
-#include "ls_internal.h"
+#include "ls_pieces.h"
 #include "fft_team.h"
 #include <math.h>
-
-// exp(j x) (see ls_fft.hip::small_rot)
-__device__ __forceinline__ float2 lst_rot(float x) {
-    if (fabsf(x) > 0.3f) {
-        float s, c;
-        sincosf(x, &s, &c);
-        return make_float2(c, s);
-    }
-    const float x2 = x * x;
-    const float c = 1.f + x2 * (-0.5f + x2 * (1.f / 24.f + x2 * (-1.f / 720.f)));
-    const float s = x * (1.f + x2 * (-1.f / 6.f + x2 * (1.f / 120.f + x2 * (-1.f / 5040.f))));
-    return make_float2(c, s);
-}
-
-struct TeamSlot {      // one register slot of the rotated reference
-    bool ok;           // slot carries a sample (else zero)
-    bool wr;           // source index wrapped around the block end
-    int off;           // clamped source offset into ref
-};
-
-// logical r[m] = ref[(m+peek) mod n] * exp(j phi((m+peek) mod n)),  m may lie outside [0, n)
-__device__ __forceinline__ TeamSlot team_slot(int m, int n, int peek, bool circular, bool want) {
-    TeamSlot s;
-    s.wr = false;
-    bool ok = want;
-    if (m >= n) { if (circular) { m -= n; s.wr = true; } else ok = false; }
-    if (m < 0) { if (circular) { m += n; s.wr = true; } else ok = false; }
-    int off = m + peek;
-    if (off >= n) { off -= n; s.wr = true; }
-    s.ok = ok;
-    s.off = ok ? off : 0;
-    return s;
-}
-
-__device__ __forceinline__ float2 team_finish(float2 raw, const TeamSlot& s, int rot, float theta32, float2 base,
-                                              float2 step) {
-    float2 v = raw;
-    if (rot) {
-        const float2 cont = cmul(base, step);
-        const float2 wrapped = lst_rot(theta32 * (float)(s.wr ? s.off : 0));
-        v = cmul(v, s.wr ? wrapped : cont);
-    }
-    return s.ok ? v : make_float2(0.f, 0.f);
-}
 
 template <bool AUTO>
 __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_team_kernel(LsFftArgs a) {
@@ -84,8 +40,8 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_team_kernel(LsFftArgs a
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int idx = 256 * r + t;
-            const TeamSlot es = team_slot(m0 + idx, n, a.peek, circ, idx < cnt + ext);
-            v[r] = team_finish(ref[es.off], es, a.rot, a.theta32, ebase, a.step[r]);
+            const LsSlot es = ls_slot(m0 + idx, n, a.peek, circ, idx < cnt + ext);
+            v[r] = ls_slot_finish(ref[es.off], es, a.rot, a.theta32, ebase, a.step[r]);
             u[r] = idx < cnt ? v[r] : make_float2(0.f, 0.f);
         }
         ft4096_fwd<0>(u, f);
@@ -116,15 +72,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_team_kernel(LsFftArgs a
     ft4096_inv<1>(wrs, f);
     // partial[b][team][0/1][lag] holds conj(g) so that the Levinson prologue's conj() restores g
     float2* __restrict__ part = a.partial + ((int64_t)b * nteams + team) * 2 * T;
-    const float sc = 1.0f / (float)FT_P;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lag = 256 * r + t;
-        if (lag < T) {
-            if (AUTO) part[lag] = make_float2(wrr[r].x * sc, -wrr[r].y * sc);
-            part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
-    }
+    ls_store_partial<FT_THREADS, AUTO>(part, wrr, wrs, T, t, 1.0f / (float)FT_P);
 }
 
 __global__ __launch_bounds__(FT_THREADS, 2) void ls_fir_team_kernel(LsFftArgs a) {
@@ -144,12 +92,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fir_team_kernel(LsFftArgs a)
 
     // H = FFT(taps zero padded) / 4096, once per team (frequency layout, registers)
     float2 h[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int idx = 256 * r + t;
-        const double2 tp = taps[idx < T ? idx : 0];
-        h[r] = idx < T ? make_float2((float)tp.x, (float)tp.y) : make_float2(0.f, 0.f);
-    }
+    ls_load_taps<FT_THREADS>(h, taps, T, t);
     ft4096_fwd<1>(h, f);
     const float sc = 1.0f / (float)FT_P;
 #pragma unroll
@@ -165,8 +108,8 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fir_team_kernel(LsFftArgs a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = mstart + 256 * r + t;
-            const TeamSlot xs = team_slot(m, n, a.peek, circ, m < n);
-            x[r] = team_finish(ref[xs.off], xs, a.rot, a.theta32, xbase, a.step[r]);
+            const LsSlot xs = ls_slot(m, n, a.peek, circ, m < n);
+            x[r] = ls_slot_finish(ref[xs.off], xs, a.rot, a.theta32, xbase, a.step[r]);
             sv[r] = srv[(m >= 0 && m < n) ? m : 0];
         }
         ft4096_fwd<0>(x, f);
@@ -196,11 +139,7 @@ int ls_team_teams_per_block(int64_t n, int T) {
 
 static void team_fill(LsFftArgs& a, double theta) {
     a.piece = FT_P - (a.T - 1);
-    a.theta32 = (float)theta;
-    for (int r = 0; r < 16; ++r) {
-        const double ang = theta * 256.0 * r;
-        a.step[r] = make_float2((float)cos(ang), (float)sin(ang));
-    }
+    ls_fill_steps(a, theta, FT_THREADS);
 }
 
 int ls_launch_corr_team(LsFftArgs a, double theta, int teams_per_block, int nblocks, bool with_autocorr,

@@ -68,12 +68,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
     const float sc = 1.0f / (float)FT_P;
     {
         float2 h[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int idx = FT_THREADS * r + t;
-            const double2 tp = taps[idx < T ? idx : 0];
-            h[r] = idx < T ? make_float2((float)tp.x, (float)tp.y) : make_float2(0.f, 0.f);
-        }
+        ls_load_taps<FT_THREADS>(h, taps, T, t);
         ft4096_fwd<1>(h, f);
 #pragma unroll
         for (int r = 0; r < 16; ++r) Hs[FT_THREADS * r] = make_float2(h[r].x * sc, h[r].y * sc);
@@ -94,43 +89,18 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
         for (int r = 0; r < 16; ++r) y[r] = ltc_cmul(xc[r], Hs[FT_THREADS * r]);
         __builtin_amdgcn_sched_barrier(0);
         {
-            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, ltc_clampu(cnt) * 8u);
+            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) sv[r] = prc_buf_load_c64(rs, vslot + 2048u * r, 0u);
         }
         // one rotation on the way out: from this bin's frame to the frame of whoever reads the stream next
-        const bool rot_out = a.rot || a.rot2;
-        float2 obase = make_float2(1.f, 0.f), ibase = make_float2(1.f, 0.f);
-        if (rot_out) {
-            const int64_t idx = (int64_t)n0 - ext + t + peek;
-            const float2 p1 = a.rot ? phase_rot(a.pr, idx) : make_float2(1.f, 0.f);
-            float2 p2 = a.rot2 ? phase_rot(a.pr2, idx) : make_float2(1.f, 0.f);
-            p2.y = -p2.y;
-            obase = cmul(p1, p2);
-            if (ROT_IN) ibase = make_float2(p1.x, -p1.y);
-        }
+        float2 obase, ibase;
+        const bool rot_out = ls_out_rotation<ROT_IN>(a, (int64_t)n0 - ext + t + peek, obase, ibase);
         __builtin_amdgcn_sched_barrier(0);
         ft4096_inv<0>(y, f);
         // last `peek` outputs of the block: rho samples whose ramp restarted carry gamma instead of 1
-        if (a.rot && peek > 0 && n0 + cnt > n - peek) {
-            const float2 g1 = a.gamma_m1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = n0 + FT_THREADS * r + t - ext;
-                const int over = nn - (n - peek);            // 0..peek-1 for affected outputs
-                if (over >= 0 && nn < n) {
-                    float2 acc = make_float2(0.f, 0.f);
-                    for (int k = 0; k <= over && k < T; ++k) {
-                        const double2 wk = taps[k];
-                        cmac(acc, make_float2((float)wk.x, (float)wk.y), ref[over - k]);   // rho[nn-k] = ref[nn-k+peek-n]
-                    }
-                    const float2 c = cmul(g1, acc);
-                    y[r].x += c.x;
-                    y[r].y += c.y;
-                }
-            }
-        }
-        const __amdgpu_buffer_rsrc_t ro = prc_rsrc(out + n0, ltc_clampu(cnt) * 8u);
+        if (a.rot) ls_gamma_edge<FT_THREADS>(y, taps, ref, a.gamma_m1, n, n0, cnt, ext, peek, T, t);
+        const __amdgpu_buffer_rsrc_t ro = prc_rsrc(out + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float2 sin_ = sv[r];
@@ -163,11 +133,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_fused_cached_team_kernel(LsF
     if (a.has_next) {
         ft4096_inv<0>(wrs, f);
         float2* __restrict__ part = a.partial + ((int64_t)b * nteams + team) * 2 * T;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lag = FT_THREADS * r + t;
-            if (lag < T) part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
+        ls_store_partial<FT_THREADS, false>(part, wrs, wrs, T, t, sc);
     }
 }
 
@@ -195,13 +161,7 @@ int ls_team_chain_teams_per_block(int64_t n, int piece, int max_blocks, int per)
 
 int ls_launch_fused_cached_team(LsFftArgs a, double theta, double theta_out, double gamma_angle, int teams_per_block,
                                 int nblocks, hipStream_t stream) {
-    ltc_fill(a, theta);
-    for (int r = 0; r < 16; ++r) {
-        const double ang_in = theta * (double)FT_THREADS * r, ang = (theta - theta_out) * (double)FT_THREADS * r;
-        a.step2[r] = make_float2((float)cos(ang_in), (float)sin(ang_in));
-        a.step[r] = make_float2((float)cos(ang), (float)sin(ang));
-    }
-    a.gamma_m1 = make_float2((float)(cos(gamma_angle) - 1.0), (float)sin(gamma_angle));
+    ls_fill_fused(a, theta, theta_out, gamma_angle, FT_THREADS);       // a.piece: set by the plan (fill_xa)
     int rc = ft_device_tables(&a.tab);
     if (rc) return rc;
     const dim3 grid((unsigned)teams_per_block, (unsigned)nblocks), block(FT_THREADS);

@@ -21,7 +21,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
     float2* __restrict__ cache = a.cache + (int64_t)b * npieces * FT_P;
     const unsigned vo8 = (unsigned)t * 8u;
     const unsigned vslot = vo8 - (unsigned)ext * 8u;          // slot idx -> piece sample idx-ext (idx<ext: out of range)
-    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, ltc_clampu(n - peek) * 8u);
+    const __amdgpu_buffer_rsrc_t rx = prc_rsrc(ref + peek, prc_clampu(n - peek) * 8u);
 
     // autocorrelation accumulator: element (r, t) is private to thread t, it only lives in LDS to save 32 VGPRs
     float2* Wrr = lds + FT_LDS_ELEMS + t;
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
         for (int r = 0; r < 16; ++r) x[r] = xn[r];
         // surveillance piece in slots [ext, ext+cnt), rotated below by e^{-j theta (n+peek)}
         {
-            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, ltc_clampu(cnt) * 8u);
+            const __amdgpu_buffer_rsrc_t rs = prc_rsrc(srv + n0, prc_clampu(cnt) * 8u);
 #pragma unroll
             for (int r = 0; r < 16; ++r) u[r] = prc_buf_load_c64(rs, vslot + 2048u * r, 0u);
         }
@@ -60,40 +60,9 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
             sbase.y = -sbase.y;
         }
         // wrapped tail of rho (source index restarts at ref[0]); unrotated, so no phase here
-        const int wstart = n - peek - mstart;
-        if (peek > 0 && wstart < FT_P) {
-            int cw = FT_P - wstart;
-            if (cw > peek) cw = peek;
-            const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref, ltc_clampu(cw) * 8u);
-            const unsigned voff = vo8 - (unsigned)wstart * 8u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float2 w = prc_buf_load_c64(rw, voff + 2048u * r, 0u);
-                x[r].x += w.x;
-                x[r].y += w.y;
-            }
-        }
+        ls_add_wrapped_tail<FT_THREADS, false>(x, ref, vo8, n - peek - mstart, peek, FT_P);
         // rho piece in slots [ext, ext+cnt): the same samples, masked by the range check
-        {
-            int cu = cnt;
-            if (n - peek - n0 < cu) cu = n - peek - n0;
-            const __amdgpu_buffer_rsrc_t ru = prc_rsrc(ref + peek + n0, ltc_clampu(cu) * 8u);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) up[r] = prc_buf_load_c64(ru, vslot + 2048u * r, 0u);
-            const int wst = n - peek - n0;                    // first wrapped sample of the piece
-            if (peek > 0 && wst < cnt) {
-                // a last piece shorter than peek starts inside the wrapped run (wst < 0): its source starts at ref[-wst]
-                const int w0 = wst > 0 ? wst : 0;
-                const __amdgpu_buffer_rsrc_t rw = prc_rsrc(ref + (w0 - wst), ltc_clampu(cnt - w0) * 8u);
-                const unsigned voff = vslot - (unsigned)w0 * 8u;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float2 w = prc_buf_load_c64(rw, voff + 2048u * r, 0u);
-                    up[r].x += w.x;
-                    up[r].y += w.y;
-                }
-            }
-        }
+        ls_load_rho_piece<FT_THREADS>(up, ref, n, peek, n0, cnt, vslot);
         __builtin_amdgcn_sched_barrier(0);
         ft4096_fwd<0>(x, f);
         {
@@ -135,19 +104,11 @@ __global__ __launch_bounds__(FT_THREADS, 2) void ls_corr_cached_team_kernel(LsFf
     ft4096_inv<1>(wrr, f);
     // partial[b][team][0/1][lag] holds conj(g): the prepare / solve prologues conjugate back
     float2* __restrict__ part = a.partial + ((int64_t)b * nteams + team) * 2 * T;
-    const float sc = 1.0f / (float)FT_P;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lag = FT_THREADS * r + t;
-        if (lag < T) {
-            part[lag] = make_float2(wrr[r].x * sc, -wrr[r].y * sc);
-            part[T + lag] = make_float2(wrs[r].x * sc, -wrs[r].y * sc);
-        }
-    }
+    ls_store_partial<FT_THREADS, true>(part, wrr, wrs, T, t, 1.0f / (float)FT_P);
 }
 
 int ls_launch_corr_cached_team(LsFftArgs a, double theta, int teams_per_block, int nblocks, hipStream_t stream) {
-    ltc_fill(a, theta);
+    ls_fill_steps(a, theta, FT_THREADS);       // a.piece: set by the plan (fill_xa)
     int rc = ft_device_tables(&a.tab);
     if (rc) return rc;
     rc = prc_lds_optin(reinterpret_cast<const void*>(&ls_corr_cached_team_kernel), (int)LTC_LDS);

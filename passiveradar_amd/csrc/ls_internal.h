@@ -1,6 +1,7 @@
 // Internal interfaces between the LS translation units.
 #pragma once
 #include "common.h"
+#include <math.h>
 
 struct LsFftArgs {
     const float2* ref;
@@ -29,6 +30,27 @@ struct LsFftArgs {
     float2 step2[16];
     float2 gamma_m1;
 };
+
+// Host side of the per-register phase steps: thread t, register r of a transform on W threads holds slot W r + t, so
+// step[r] = exp(j theta W r) (a.piece is the caller's: the plan or the unit's own piece rule)
+static inline void ls_fill_steps(LsFftArgs& a, double theta, int W) {
+    a.theta32 = (float)theta;
+    for (int r = 0; r < 16; ++r) {
+        const double ang = theta * (double)W * r;
+        a.step[r] = make_float2((float)cos(ang), (float)sin(ang));
+    }
+}
+// the same for the fused kernels: step2[] takes the input into bin i's frame, step[] the output from it into the next
+// reader's (theta_out), gamma_m1 = gamma - 1 for the last peek outputs
+static inline void ls_fill_fused(LsFftArgs& a, double theta, double theta_out, double gamma_angle, int W) {
+    ls_fill_steps(a, theta - theta_out, W);
+    a.theta32 = (float)theta;
+    for (int r = 0; r < 16; ++r) {
+        const double ang_in = theta * (double)W * r;
+        a.step2[r] = make_float2((float)cos(ang_in), (float)sin(ang_in));
+    }
+    a.gamma_m1 = make_float2((float)(cos(gamma_angle) - 1.0), (float)sin(gamma_angle));
+}
 
 // time-domain FIR of ls.hip on the circulant data matrix: out = srv - A taps (taps [nblocks][T] complex128, which the kernel
 // rounds to float32)

@@ -1,14 +1,12 @@
 // Shared by the two translation units of the cached-spectrum chain on the 4096-point team transform
 // (ls_fft_team_corr_cached.hip, ls_fft_team_cached.hip): they are compiled with different twiddle storage (Makefile).
 #pragma once
-#include "ls_internal.h"
+#include "ls_pieces.h"
 #include "fft_team.h"
 #include <math.h>
 
 #define LTC_SPEC FT_P                        // float2 of per-thread spectrum kept in LDS behind the transform's area
 static constexpr size_t LTC_LDS = sizeof(float2) * (FT_LDS_ELEMS + LTC_SPEC);
-
-__device__ __forceinline__ unsigned ltc_clampu(int x) { return x < 0 ? 0u : (unsigned)x; }
 
 __device__ __forceinline__ void ltc_cmac_bconj(float2& w, float2 u, float2 x) {   // w += u * conj(x)
 #ifdef FT_PK
@@ -16,10 +14,7 @@ __device__ __forceinline__ void ltc_cmac_bconj(float2& w, float2 u, float2 x) { 
     pk_cmac_bconj(ww, pk_from(u), pk_from(x));
     w = pk_to(ww);
 #else
-    w.x = fmaf(u.x, x.x, w.x);
-    w.x = fmaf(u.y, x.y, w.x);
-    w.y = fmaf(u.y, x.x, w.y);
-    w.y = fmaf(-u.x, x.y, w.y);
+    cmac_conj(w, u, x);
 #endif
 }
 
@@ -63,12 +58,4 @@ static inline int ltc_piece(int T, int align) {
 // stores of the previous piece (vmcnt counts loads and stores in order on gfx9).  tools/ubench/stream4.hip: +5 % of HBM rate.
 __device__ __forceinline__ void ltc_loads_landed() {
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt and lgkmcnt untouched
-}
-
-static inline void ltc_fill(LsFftArgs& a, double theta) {      // a.piece: set by the plan (fill_xa)
-    a.theta32 = (float)theta;
-    for (int r = 0; r < 16; ++r) {
-        const double ang = theta * (double)FT_THREADS * r;
-        a.step[r] = make_float2((float)cos(ang), (float)sin(ang));
-    }
 }

@@ -472,6 +472,26 @@ def test_ls_team_chain_last_piece_shorter_than_peek(tail):
         cr.set_default_ls_method(0)
 
 
+@pytest.mark.parametrize("L,P,tail", [(800, 4097, 5), (200, 1025, 7)])
+def test_ls_per_bin_fft_kernels_ragged_tail_far_bins(L, P, tail):
+    """the per-bin FFT kernels (a block too short for the cached chain) on the 4096- and on the 1024-point transform: two
+    full pieces of P - T samples and a tail shorter than peek, so the run of wrapped reference samples straddles the last
+    two pieces; rotated bins whose phase over the peek wrapped samples (2 pi 60 / 1e4 * 10 = 0.38 rad) leaves the Taylor
+    range of the wrapped-sample rotation"""
+    from passiveradar_amd import clutter_removal as cr
+    fs, bins = 1.0e4, [60.0, 0.0, -60.0]
+    n = 2 * (P - (L + 10)) + tail
+    ref, srv = scene.make_scene(n, fs, 50, 97531 + L)
+    cr.set_default_ls_method(2)
+    try:
+        got = cr.LS_Filter_Multiple(ref, srv, L, fs, bins)
+    finally:
+        cr.set_default_ls_method(0)
+    e = rel_err(got, O.LS_Filter_Multiple(ref, srv, L, fs, bins))
+    print(f"per-bin FFT kernels, L = {L}, n = {n}: {e:.2e}")
+    assert e < TOL
+
+
 def test_library_first_then_torch_in_a_fresh_process():
     """import order must not matter: libprcore used before torch is imported (fresh interpreter), then torch must
     still see the GPU and the device-tensor path must agree with the NumPy path (one HIP runtime per process)"""
