@@ -34,7 +34,7 @@
  *     depends on what a plan, a caller's workspace or the library's scratch was used for before
  *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
- *     prc_normalize).
+ *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -51,7 +51,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 670   /* 670: prc_ls_svd_workspace_bytes, prc_ls_svd_execute, prc_ls_svd_set_profiling, prc_ls_svd_get_profile (LS_Filter_SVD
+#define PRC_VERSION 680   /* 680: prc_patch_desc, prc_patch, prc_patch_peak, prc_xambg_patch_workspace_bytes, prc_xambg_patch, prc_xambg_patch_peaks
+                             (exact, un-decimated cross-ambiguity patches and sub-cell peak refinement on device);
+                             670: prc_ls_svd_workspace_bytes, prc_ls_svd_execute, prc_ls_svd_set_profiling, prc_ls_svd_get_profile (LS_Filter_SVD
                              on device);
                              660: prc_firdec_desc, prc_fir_decimate, prc_shift, prc_normalize_workspace_bytes, prc_normalize (the rest of
                              signal_utils.py on device: decimate, channel_preprocessing, shift, offset_compensation, normalize);
@@ -690,6 +692,71 @@ int prc_shift(const void* x, void* y, int64_t rows, int64_t row_bytes, int64_t s
  * synchronises.  y may be x.  PRC_EINVAL: null pointers, n < 1, is_complex not 0 / 1. */
 int prc_normalize_workspace_bytes(int64_t n, size_t* bytes);
 int prc_normalize(const void* x, void* y, int64_t n, int32_t is_complex, void* workspace, void* stream);
+
+/* ---- exact cross-ambiguity patches ("zoom") and sub-cell peak refinement ------------------------------------------------ */
+/* The un-decimated cross-ambiguity function on small lag x Doppler patches placed anywhere, at any Doppler spacing.  For a
+ * frame of n samples and a patch (frame, lag0, doppler0):
+ *   X[d][l] = sum_{i < n} w[i] ref[i] conj(srv[idx(i + lag0 + l)]) exp(+j 2 pi (doppler0 + d doppler_step) i / sample_rate),
+ *   d < ndoppler, l < nlags;  wrap = 1: idx(m) = m mod n (true modulus, negative lags allowed: the np.roll convention of
+ *   fast_xambg);  wrap = 0: terms with m outside [0, n) are dropped (the convention of prc_xcorr / direct_xambg).
+ * An echo srv[i] = ref[i - D] exp(+j 2 pi f i / Fs) peaks at lag D, Doppler +f (direct_xambg's row sense, the mirror of
+ * fast_xambg's rows); cell (row, col) of a fast_xambg surface is lag R - col, Doppler (F/2 - row) / CPI.
+ * ref, srv: DEVICE complex64, frame b at element b * frame_stride; window: DEVICE float32[n] shared by the frames, or NULL;
+ * patches: DEVICE prc_patch[npatches] (a detector can write it on the device; nothing returns to the host);
+ * out: DEVICE complex64 [npatches][ndoppler][nlags].
+ * Arithmetic: the phase is exact -- no float32 ramp over i.  A workgroup takes 1024-sample tiles of one (patch, 64 lags --
+ * 16 when nlags <= 32 --, 16 Dopplers); inside a tile every 16 samples are one float32 Horner run acc = acc conj(z) + p over the lag product p, and
+ * each run is rotated by a phasor whose argument frac(f i / Fs) was reduced in float64; runs add in float32 inside a tile,
+ * tiles in float64; the per-workgroup sums go to `workspace` and a second kernel adds them in float64 in a fixed order and
+ * rounds to complex64 once.  No atomics: two calls give the same bits, whatever the workspace held.  Error <= 1e-6 of
+ * ||w ref||_2 ||srv||_2 (DESIGN.md section 17 has the measured figures).
+ * A patch whose frame is outside [0, nframes), whose |lag0| >= n or whose doppler0 is not finite is skipped on the device:
+ * its cells are written as zeros and nothing is read for it.
+ * Memory: frame b of ref / srv is read only inside [b * frame_stride, b * frame_stride + n), the window inside [0, n), the
+ * npatches records of the list; every cell of out is written and nothing else is, but the workspace
+ * (prc_xambg_patch_workspace_bytes bytes, DEVICE, 16-byte aligned, not shared by calls in flight).
+ * prc_xambg_patch_peaks, one wavefront per patch: the argmax of |X|^2 (float64 from the stored complex64 cells; the first
+ * cell in [d][l] order wins ties), then along each axis a 3-point parabola on |X|: off = (y- - y+) / (2 (y- - 2 y0 + y+)),
+ * clamped to +-1/2, 0 when the denominator is 0; lag = lag0 + l + off_l, doppler = doppler0 + (d + off_d) doppler_step.
+ * flags: bit 0 = the argmax is on a Doppler edge of the patch (d = 0 or ndoppler - 1): no Doppler interpolation; bit 1 = the
+ * same for the lag axis; bit 2 = a flat patch (all |X|^2 equal, dead air included): cell (0, 0), offsets 0, never a NaN.
+ * Two kernels (patch) / one kernel (peaks) on `stream`; neither allocates, copies nor synchronises (both can be captured).
+ * PRC_EINVAL: a bad descriptor header, null pointers (window excepted), n < 1, nframes < 1, frame_stride < n with more than
+ * one frame, nlags outside 1 .. 1024, ndoppler outside 1 .. 4096, wrap not 0 / 1, a sample_rate or doppler_step that is not
+ * finite, sample_rate == 0, npatches < 0.  npatches == 0 is a no-op.  (prc_xambg_patch_peaks reads only nlags, ndoppler and
+ * doppler_step of the descriptor.)  prc_xambg_patch_workspace_bytes is host arithmetic and needs no device. */
+typedef struct prc_patch_desc {
+    uint32_t struct_size;  /* sizeof(prc_patch_desc) as the host compiled it (see Conventions)             */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int64_t n;             /* samples per frame                                                       */
+    int64_t frame_stride;  /* elements between frames of ref / srv (>= n when nframes > 1)            */
+    int32_t nframes;       /* frames in the stack                                                     */
+    int32_t nlags;         /* 1 .. 1024 lags per patch                                                */
+    int32_t ndoppler;      /* 1 .. 4096 Doppler rows per patch                                        */
+    int32_t wrap;          /* 1: circular lags (fast_xambg), 0: terms outside the frame dropped       */
+    double sample_rate;    /* Hz                                                                      */
+    double doppler_step;   /* Hz between Doppler rows of a patch                                      */
+} prc_patch_desc;
+#define PRC_PATCH_DESC_SIZE_680 56u
+#define PRC_PATCH_MAX_LAGS 1024
+#define PRC_PATCH_MAX_DOPPLER 4096
+typedef struct prc_patch {       /* 16 bytes */
+    int32_t frame;         /* index into the stack                                                    */
+    int32_t lag0;          /* lag of column 0, samples, |lag0| < n                                    */
+    double doppler0;       /* Doppler of row 0, Hz                                                    */
+} prc_patch;
+typedef struct prc_patch_peak {  /* 32 bytes */
+    double lag;            /* samples, sub-cell                                                       */
+    double doppler;        /* Hz, sub-cell                                                            */
+    float amplitude;       /* |X| at the argmax cell                                                  */
+    int32_t d, l;          /* the argmax cell                                                         */
+    uint32_t flags;        /* bit 0: Doppler edge, bit 1: lag edge, bit 2: flat patch                 */
+} prc_patch_peak;
+int prc_xambg_patch_workspace_bytes(const prc_patch_desc* desc, int32_t npatches, size_t* bytes);
+int prc_xambg_patch(const prc_patch_desc* desc, const void* ref, const void* srv, const float* window /* or NULL */,
+                    const prc_patch* patches, int32_t npatches, void* out, void* workspace, void* stream);
+int prc_xambg_patch_peaks(const prc_patch_desc* desc, const prc_patch* patches, int32_t npatches, const void* X,
+                          prc_patch_peak* peaks, void* stream);
 
 #ifdef __cplusplus
 }

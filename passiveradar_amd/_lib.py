@@ -120,6 +120,28 @@ class FirdecDesc(_Desc):
                 ("fc", C.c_double), ("fs", C.c_double), ("phase_offset", C.c_double)]
 
 
+class PatchDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("n", C.c_int64), ("frame_stride", C.c_int64), ("nframes", C.c_int32), ("nlags", C.c_int32),
+                ("ndoppler", C.c_int32), ("wrap", C.c_int32), ("sample_rate", C.c_double), ("doppler_step", C.c_double)]
+
+
+class Patch(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("lag0", C.c_int32), ("doppler0", C.c_double)]
+
+
+class PatchPeak(C.Structure):
+    _fields_ = [("lag", C.c_double), ("doppler", C.c_double), ("amplitude", C.c_float), ("d", C.c_int32), ("l", C.c_int32),
+                ("flags", C.c_uint32)]
+
+
+# NumPy views of prc_patch / prc_patch_peak (same layout as the ctypes mirrors)
+PATCH_DTYPE = np.dtype([("frame", "<i4"), ("lag0", "<i4"), ("doppler0", "<f8")])
+PATCH_PEAK_DTYPE = np.dtype([("lag", "<f8"), ("doppler", "<f8"), ("amplitude", "<f4"), ("d", "<i4"), ("l", "<i4"),
+                             ("flags", "<u4")])
+PATCH_MAX_LAGS, PATCH_MAX_DOPPLER = 1024, 4096       # PRC_PATCH_MAX_LAGS, PRC_PATCH_MAX_DOPPLER
+PATCH_EDGE_DOPPLER, PATCH_EDGE_LAG, PATCH_FLAT = 1, 2, 4   # prc_patch_peak.flags
+
 FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
 
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
@@ -131,7 +153,7 @@ PERSISTENCE_TERMS_PER_LAUNCH = 256
 DISPLAY_PLOT, DISPLAY_STORED = 0, 1   # prc_display_orient
 
 
-MIN_LIB_VERSION = 670      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
+MIN_LIB_VERSION = 680      # PRC_VERSION of include/prcore.h these ctypes declarations mirror
 
 RAW_DTYPES = {"int8": 0, "uint8": 1, "int16": 2, "float32": 3, "complex64": 4}
 
@@ -230,6 +252,10 @@ _SIGNATURES = {
     "prc_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "prc_normalize_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "prc_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "prc_xambg_patch_workspace_bytes": (C.c_int, [C.POINTER(PatchDesc), C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_xambg_patch": (C.c_int, [C.POINTER(PatchDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "prc_xambg_patch_peaks": (C.c_int, [C.POINTER(PatchDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),

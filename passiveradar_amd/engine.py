@@ -333,6 +333,54 @@ def ls_svd_get_profile():
     return tuple(ms), k.value
 
 
+def patch_desc(n, nlags, ndoppler, sample_rate, doppler_step, wrap=True, nframes=1, frame_stride=None):
+    """prc_patch_desc of include/prcore.h"""
+    d = _lib.PatchDesc()
+    d.n, d.frame_stride, d.nframes = int(n), int(n if frame_stride is None else frame_stride), int(nframes)
+    d.nlags, d.ndoppler, d.wrap = int(nlags), int(ndoppler), int(bool(wrap))
+    d.sample_rate, d.doppler_step = float(sample_rate), float(doppler_step)
+    return d
+
+
+def xambg_patch_workspace_bytes(desc, npatches):
+    """device bytes prc_xambg_patch needs in ``workspace`` for ``npatches`` patches of desc's shape"""
+    nb = C.c_size_t(0)
+    check(lib().prc_xambg_patch_workspace_bytes(C.byref(desc), int(npatches), C.byref(nb)))
+    return int(nb.value)
+
+
+def xambg_patch_execute(desc, ref, srv, window, patches, npatches, out, workspace, stream=None):
+    """exact cross-ambiguity patches (device buffers or torch tensors; ``patches``: DEVICE prc_patch records)"""
+    check(lib().prc_xambg_patch(C.byref(desc), _ptr(ref), _ptr(srv), _ptr(window), _ptr(patches), int(npatches), _ptr(out),
+                                _ptr(workspace), stream))
+
+
+def xambg_patch_peaks(desc, patches, npatches, X, peaks, stream=None):
+    """argmax + parabolic refinement per patch (``peaks``: DEVICE prc_patch_peak records)"""
+    check(lib().prc_xambg_patch_peaks(C.byref(desc), _ptr(patches), int(npatches), _ptr(X), _ptr(peaks), stream))
+
+
+def patch_list(lags, dopplers, frame=None, nframes=1, n=None):
+    """HOST prc_patch records from patch origins, validated as the header asks of a host-built list: ValueError for a
+    frame outside [0, nframes), |lag0| >= n or a Doppler that is not finite"""
+    lags = np.atleast_1d(np.asarray(lags))
+    dopplers = np.atleast_1d(np.asarray(dopplers, dtype=np.float64))
+    if lags.ndim != 1 or lags.shape != dopplers.shape:
+        raise ValueError("lags and dopplers must be one-dimensional and of the same length")
+    if lags.size and not np.all(lags == np.rint(lags)):
+        raise ValueError("patch lags are whole samples")
+    frames = np.zeros(lags.shape, np.int64) if frame is None else np.broadcast_to(np.asarray(frame, dtype=np.int64), lags.shape)
+    if np.any(frames < 0) or np.any(frames >= nframes):
+        raise ValueError(f"patch frame outside [0, {nframes})")
+    if n is not None and np.any(np.abs(lags.astype(np.int64)) >= n):
+        raise ValueError(f"patch lag origin outside (-{n}, {n})")
+    if not np.all(np.isfinite(dopplers)):
+        raise ValueError("patch Doppler origins must be finite")
+    rec = np.zeros(lags.shape[0], dtype=_lib.PATCH_DTYPE)
+    rec["frame"], rec["lag0"], rec["doppler0"] = frames, lags.astype(np.int64), dopplers
+    return rec
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

@@ -13,7 +13,8 @@ import numpy as np
 
 from . import _lib, engine
 
-__all__ = ["fast_xambg", "fast_xambg_multi", "direct_xambg", "caf_plan_for", "set_default_methods"]
+__all__ = ["fast_xambg", "fast_xambg_multi", "direct_xambg", "caf_plan_for", "set_default_methods", "xambg_patch",
+           "patch_origins"]
 
 # Kernel selection used by fast_xambg (0 = let the plan decide).  Not part of the reference
 # signature; tests flip it to run the same cases through every kernel family.
@@ -210,3 +211,100 @@ def fast_xambg_multi(refChannels, srvChannel, rangeBins, freqBins, inputLen=None
     plan.execute_multi([d_refs.ptr + 8 * n_in * i for i in range(nref)], d_srv,
                        [d_outs.ptr + 8 * F * (R + 1) * i for i in range(nref)], 1, n, n_in, d_win)
     return [d_outs.download((F, R + 1, 1), np.complex64, offset_bytes=8 * F * (R + 1) * i) for i in range(nref)]
+
+
+def patch_origins(rows, cols, rangeBins, freqBins, n, sampleRate, nlags, ndoppler, doppler_step):
+    """(lags, dopplers): the origins that centre an ``ndoppler`` x ``nlags`` patch of spacing ``doppler_step`` on the
+    ``fast_xambg`` cells (rows, cols).  Cell (row, col) is lag rangeBins - col and -- rows are mirrored and fftshift-ed --
+    Doppler (freqBins/2 - row) / CPI (scene.expected_peak_cell is the inverse); the centre is patch cell
+    (ndoppler // 2, nlags // 2).  Host arithmetic only."""
+    rows = np.atleast_1d(np.asarray(rows, dtype=np.int64))
+    cols = np.atleast_1d(np.asarray(cols, dtype=np.int64))
+    cpi = n / float(sampleRate)
+    lags = (int(rangeBins) - cols) - int(nlags) // 2
+    dopplers = (0.5 * int(freqBins) - rows) / cpi - (int(ndoppler) // 2) * float(doppler_step)
+    return lags, dopplers
+
+
+def xambg_patch(refChannel, srvChannel, sampleRate, lags, dopplers, nlags=16, ndoppler=16, doppler_step=None, window=None,
+                wrap=True, frame=None):
+    """Exact (un-decimated) cross-ambiguity function on lag x Doppler patches -- the "zoom" step after a detector:
+
+        X[p, d, l] = sum_i w[i] ref[i] conj(srv[idx(i + lags[p] + l)]) exp(+j 2 pi (dopplers[p] + d doppler_step) i / sampleRate)
+
+    ``wrap=True``: idx(m) = m mod n (fast_xambg's np.roll convention, negative lags allowed); ``wrap=False``: terms outside
+    the frame are dropped (direct_xambg / xcorr).  An echo srv[i] = ref[i - D] exp(+j 2 pi f i / Fs) peaks at lag D, Doppler
+    +f: direct_xambg's row sense, the mirror of fast_xambg's rows (``patch_origins`` maps fast_xambg cells to origins).  No
+    decimator, so no droop, and the phase is exact (no float32 ramp): prc_xambg_patch of include/prcore.h.
+
+    Channels are 1-D or [nframes, n] stacks, NumPy (staged) or torch device tensors (zero copy, on torch's current stream,
+    nothing returns to the host; a row-strided view is taken as it is).  ``frame``: frame index per patch (default 0).
+    ``doppler_step=None``: 0.25 sampleRate / n, a quarter of a fast_xambg cell.  ``window``: as fast_xambg's.
+    Returns complex64 [npatches, ndoppler, nlags]."""
+    if tuple(refChannel.shape) != tuple(srvChannel.shape):
+        raise ValueError("Input vectors must have the same length")
+    if len(refChannel.shape) not in (1, 2):
+        raise ValueError("xambg_patch takes one-dimensional channels or [nframes, n] stacks")
+    n = int(refChannel.shape[-1])
+    nframes = 1 if len(refChannel.shape) == 1 else int(refChannel.shape[0])
+    if n < 1 or nframes < 1:
+        raise ValueError("xambg_patch: empty channels")
+    nlags, ndoppler = int(nlags), int(ndoppler)
+    step = 0.25 * float(sampleRate) / n if doppler_step is None else float(doppler_step)
+    if isinstance(window, (tuple, str)):
+        window = _named_window(window, n)
+    elif window is not None and not _lib.is_device_tensor(window):
+        window = np.ascontiguousarray(window, dtype=np.float32)
+    if window is not None and (len(window.shape) != 1 or window.shape[0] != n):
+        raise ValueError(f"operands could not be broadcast together with shapes ({n},) {tuple(window.shape)}")
+    rec = engine.patch_list(lags, dopplers, frame, nframes, n)
+    npatches = rec.shape[0]
+    if _lib.is_device_tensor(refChannel):
+        import torch
+        with torch.cuda.device(refChannel.device):
+            st = _lib.torch_stream_ptr(refChannel.device)
+            ref = refChannel.to(torch.complex64)
+            srv = srvChannel.to(device=ref.device, dtype=torch.complex64)
+            stride = n
+            if nframes > 1:
+                # one stride for both: a row-strided view of a larger buffer stays where it is
+                if not (ref.stride(1) == 1 and srv.stride(1) == 1 and ref.stride(0) == srv.stride(0) and ref.stride(0) >= n):
+                    ref, srv = ref.contiguous(), srv.contiguous()
+                stride = ref.stride(0)
+            else:
+                ref, srv = ref.contiguous(), srv.contiguous()
+            desc = engine.patch_desc(n, nlags, ndoppler, sampleRate, step, wrap, nframes, stride)
+            nws = engine.xambg_patch_workspace_bytes(desc, npatches)
+            out = torch.empty((npatches, ndoppler, nlags), dtype=torch.complex64, device=ref.device)
+            if npatches == 0:
+                return out
+            win = None
+            if window is not None:
+                win = window if _lib.is_device_tensor(window) else torch.from_numpy(window)
+                win = win.to(device=ref.device, dtype=torch.float32).contiguous()
+            d_rec = torch.from_numpy(rec.view(np.uint8)).to(ref.device)
+            ws = torch.empty(nws, dtype=torch.uint8, device=ref.device)
+            engine.xambg_patch_execute(desc, ref, srv, win, d_rec, npatches, out, ws, st)
+        return out
+    ref = np.ascontiguousarray(refChannel, dtype=np.complex64)
+    srv = np.ascontiguousarray(srvChannel, dtype=np.complex64)
+    desc = engine.patch_desc(n, nlags, ndoppler, sampleRate, step, wrap, nframes, n)
+    nws = engine.xambg_patch_workspace_bytes(desc, npatches)
+    if npatches == 0:
+        return np.zeros((0, ndoppler, nlags), np.complex64)
+    _lib.require_gpu()
+    st = engine.staging()
+    d_ref = st.get("xp_ref", ref.nbytes)
+    d_srv = st.get("xp_srv", srv.nbytes)
+    d_rec = st.get("xp_rec", rec.nbytes)
+    d_out = st.get("xp_out", 8 * npatches * ndoppler * nlags)
+    d_ws = st.get("xp_ws", nws)
+    d_ref.upload(ref)
+    d_srv.upload(srv)
+    d_rec.upload(rec.view(np.uint8))
+    d_win = None
+    if window is not None:
+        d_win = st.get("xp_win", 4 * n)
+        d_win.upload(window)
+    engine.xambg_patch_execute(desc, d_ref, d_srv, d_win, d_rec, npatches, d_out, d_ws)
+    return d_out.download((npatches, ndoppler, nlags), np.complex64)

@@ -15,7 +15,7 @@ from ._lib import check, lib
 
 __all__ = ["CFAR_2D", "CFAR_2D_abs", "get_measurements", "multitarget_tracker", "track_maps",
            "kalman_filter_dtype", "target_track_dtype", "simple_target_tracker", "simple_track_maps",
-           "target_track_dtype_simple"]
+           "target_track_dtype_simple", "refine_peaks"]
 
 
 def CFAR_2D(X, fw, gw, thresh=None):
@@ -432,3 +432,45 @@ def simple_track_maps(xambg, rangeExtent, dopplerExtent, fw=18, gw=4):
     rec = _strack_run(do.ptr, nframes, H, W, _lib.REAL_F32, rangeExtent, dopplerExtent, None,
                       lambda nb: _lib.DeviceBuffer(nb), None)
     return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
+
+
+# ---- sub-cell peak refinement of exact ambiguity patches (range_doppler_processing.xambg_patch) ------------------------
+def refine_peaks(X, lags, dopplers, doppler_step):
+    """Per patch of ``X`` (complex64 [npatches, ndoppler, nlags], from ``xambg_patch`` with origins ``lags`` / ``dopplers``
+    and spacing ``doppler_step``): the argmax of |X|^2 (the first cell in [d][l] order wins ties) and a 3-point parabola on
+    |X| along each axis, off = (y- - y+) / (2 (y- - 2 y0 + y+)) clamped to +-1/2 (prc_xambg_patch_peaks of
+    include/prcore.h, one wavefront per patch).  Fields: ``lag`` (samples), ``doppler`` (Hz), ``amplitude`` (|X| at the
+    argmax cell), ``d``, ``l`` (the cell), ``flags`` (bit 0: the argmax is on a Doppler edge, that axis is not interpolated;
+    bit 1: the same for lag; bit 2: a flat patch, dead air included: cell (0, 0), offsets 0).
+    Returns a structured array (_lib.PATCH_PEAK_DTYPE) for NumPy input; for a torch device tensor a dict of device tensors
+    by field name (nothing returns to the host)."""
+    if len(X.shape) != 3:
+        raise ValueError("refine_peaks takes patches [npatches, ndoppler, nlags]")
+    npatches, ndoppler, nlags = (int(v) for v in X.shape)
+    rec = engine.patch_list(lags, dopplers)
+    if rec.shape[0] != npatches:
+        raise ValueError(f"{npatches} patches but {rec.shape[0]} origins")
+    desc = engine.patch_desc(1, nlags, ndoppler, 1.0, doppler_step)
+    if _lib.is_device_tensor(X):
+        import torch
+        with torch.cuda.device(X.device):
+            x = X.to(torch.complex64).contiguous()
+            raw = torch.empty((npatches, _lib.PATCH_PEAK_DTYPE.itemsize), dtype=torch.uint8, device=x.device)
+            d_rec = torch.from_numpy(rec.view(np.uint8)).to(x.device)
+            if npatches:
+                engine.xambg_patch_peaks(desc, d_rec, npatches, x, raw, _lib.torch_stream_ptr(x.device))
+        f64, f32, i32 = raw.view(torch.float64), raw.view(torch.float32), raw.view(torch.int32)
+        return {"lag": f64[:, 0], "doppler": f64[:, 1], "amplitude": f32[:, 4], "d": i32[:, 5], "l": i32[:, 6],
+                "flags": i32[:, 7]}
+    x = np.ascontiguousarray(X, dtype=np.complex64)
+    if npatches == 0:
+        return np.zeros(0, dtype=_lib.PATCH_PEAK_DTYPE)
+    _lib.require_gpu()
+    st = engine.staging()
+    d_x = st.get("xp_out", x.nbytes)
+    d_rec = st.get("xp_rec", rec.nbytes)
+    d_pk = st.get("xp_peaks", npatches * _lib.PATCH_PEAK_DTYPE.itemsize)
+    d_x.upload(x)
+    d_rec.upload(rec.view(np.uint8))
+    engine.xambg_patch_peaks(desc, d_rec, npatches, d_x, d_pk)
+    return d_pk.download((npatches,), _lib.PATCH_PEAK_DTYPE)
