@@ -34,7 +34,8 @@
  *     depends on what a plan, a caller's workspace or the library's scratch was used for before
  *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
- *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks).
+ *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
+ *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -51,7 +52,10 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680: prc_patch_desc, prc_patch, prc_patch_peak, prc_xambg_patch_workspace_bytes, prc_xambg_patch, prc_xambg_patch_peaks
+#define PRC_VERSION 680   /* 680, second edition (additions only, no layout of 680 changed, so the number stays: a host checks for the new
+                             entry points by symbol): prc_cfar_os_desc, prc_cfar_training_cells, prc_cfar_os_workspace_bytes, prc_cfar_os
+                             (order-statistic CFAR on CFAR_2D's window, on device);
+                             680: prc_patch_desc, prc_patch, prc_patch_peak, prc_xambg_patch_workspace_bytes, prc_xambg_patch, prc_xambg_patch_peaks
                              (exact, un-decimated cross-ambiguity patches and sub-cell peak refinement on device);
                              670: prc_ls_svd_workspace_bytes, prc_ls_svd_execute, prc_ls_svd_set_profiling, prc_ls_svd_get_profile (LS_Filter_SVD
                              on device);
@@ -406,6 +410,45 @@ int prc_cfar2d(const float* X, int32_t H, int32_t W, int32_t fw, int32_t gw, int
  * [nframes][H][W] themselves, |X| (hypotf, as np.abs) taken while the tiles are loaded -- one read of the complex map */
 int prc_cfar2d_c64(const void* X, int32_t H, int32_t W, int32_t fw, int32_t gw, int32_t use_thresh,
                    float thresh, float* out, int32_t nframes, void* stream);
+
+/* ---- order-statistic CFAR (OS-CFAR, Rohling) on CFAR_2D's window: DESIGN.md section 18 -------- */
+/* The training set of cell (i, j) is X[(i + c - a) mod H, (j + c - b) mod W] for (a, b) in [0, fw)^2 outside the guard block
+ * [e1, e2)^2, c = (fw-1)/2, e1 = max((fw-gw)/2, 0), e2 = min(fw-e1+1, fw): the taps of prc_cfar2d, even-fw asymmetry and
+ * wrap-around (more than once when fw > H or fw > W; cells then repeat) included.  Nt = fw^2 - (e2-e1)^2 training cells
+ * (prc_cfar_training_cells: 299 at (18, 4)).  The noise estimate z(i, j) is the rank-th smallest (1-based) of the Nt values,
+ * selected exactly by value over all finite float32 inputs (negative ones included, -0 == +0), stored as z + 0.0f (never -0).
+ * A NaN in X leaves the cells whose window holds it unspecified; nothing hangs and nothing is written elsewhere.
+ *   scale PRC_CFAR_SCALE_REFERENCE: out = (X / mean|X|) / (z + 1e-10f) -- prc_cfar2d's form with z for the box mean, mean|X|
+ *     from the same partial sums (an all-zero frame gives NaN, as there);
+ *   scale PRC_CFAR_SCALE_PLAIN: out = X / z, IEEE float32, no epsilon, no mean pass (0/0 = NaN, x/0 = inf).
+ * use_thresh != 0: out = 1.0f where the ratio > thresh, else 0.0f (NaN gives 0).  noise (or NULL): the z map.
+ * X: DEVICE float32 (input = 0) or complex64 (input = 1: |X| = hypotf on the tile load, as prc_cfar2d_c64) [nframes][H][W];
+ * out, noise: DEVICE float32 [nframes][H][W].  workspace: DEVICE, prc_cfar_os_workspace_bytes bytes (the mean partials of
+ * the reference scale, 4-byte aligned, not shared by calls in flight; 0 bytes for the plain scale, workspace may then be NULL).
+ * One kernel (plain) or two (reference) on `stream`; the call allocates, frees, copies and synchronises nothing (it can be
+ * captured).  Memory: frame f of X is read only inside [f H W, (f+1) H W); only out, noise and the workspace are written;
+ * element alignment suffices; a frame's result does not depend on its position in the stack or on the other frames.
+ * PRC_EINVAL: a bad descriptor header, null X / out, a null workspace with the reference scale, sizes that are not positive,
+ * gw < 0, Nt == 0, rank outside 0 .. Nt, a scale or input that is not listed.  PRC_EUNSUPPORTED: the 16 x 64 tile with its
+ * halo does not fit 64 KiB of LDS, 4 (fw + 15) ((fw + 69) & ~3) bytes: fw <= 90 works (the same kind of limit as
+ * prc_cfar2d's).  prc_cfar_training_cells and prc_cfar_os_workspace_bytes are host arithmetic and need no device. */
+enum prc_cfar_scale { PRC_CFAR_SCALE_REFERENCE = 0, PRC_CFAR_SCALE_PLAIN = 1 };
+typedef struct prc_cfar_os_desc {
+    uint32_t struct_size;  /* sizeof(prc_cfar_os_desc) as the host compiled it (see Conventions)     */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int32_t H, W;          /* Doppler rows, range columns of a frame                                  */
+    int32_t fw, gw;        /* window and guard widths, as CFAR_2D takes them                          */
+    int32_t rank;          /* 1 .. Nt; 0 = ceil(0.75 Nt)                                              */
+    int32_t scale;         /* prc_cfar_scale                                                          */
+    int32_t input;         /* 0 = float32 magnitudes, 1 = complex64 maps                              */
+    int32_t use_thresh;    /* != 0: out is 1.0f / 0.0f for ratio > thresh                             */
+    float thresh;
+} prc_cfar_os_desc;
+#define PRC_CFAR_OS_DESC_SIZE_MIN 44u
+int prc_cfar_training_cells(int32_t fw, int32_t gw, int32_t* ncells);
+int prc_cfar_os_workspace_bytes(const prc_cfar_os_desc* desc, int32_t nframes, size_t* bytes);
+int prc_cfar_os(const prc_cfar_os_desc* desc, const void* X, float* out, float* noise /* or NULL */, int32_t nframes,
+                void* workspace, void* stream);
 
 /* ---- channel offset estimation (SURVEY 8f "next" #2): signal_utils.py:73-78 ------------------- */
 /* The zero-phase IIR decimator of scipy.signal.decimate(x, q) (ftype 'iir', zero_phase=True:

@@ -142,6 +142,16 @@ PATCH_PEAK_DTYPE = np.dtype([("lag", "<f8"), ("doppler", "<f8"), ("amplitude", "
 PATCH_MAX_LAGS, PATCH_MAX_DOPPLER = 1024, 4096       # PRC_PATCH_MAX_LAGS, PRC_PATCH_MAX_DOPPLER
 PATCH_EDGE_DOPPLER, PATCH_EDGE_LAG, PATCH_FLAT = 1, 2, 4   # prc_patch_peak.flags
 
+
+class CfarOsDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("H", C.c_int32), ("W", C.c_int32), ("fw", C.c_int32), ("gw", C.c_int32), ("rank", C.c_int32),
+                ("scale", C.c_int32), ("input", C.c_int32), ("use_thresh", C.c_int32), ("thresh", C.c_float)]
+
+
+CFAR_SCALE_REFERENCE, CFAR_SCALE_PLAIN = 0, 1      # prc_cfar_scale
+CFAR_SCALES = {"reference": CFAR_SCALE_REFERENCE, "plain": CFAR_SCALE_PLAIN}
+
 FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
 
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
@@ -223,6 +233,9 @@ _SIGNATURES = {
                              C.c_void_p, C.c_int32, C.c_void_p]),
     "prc_cfar2d_c64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                  C.c_void_p, C.c_int32, C.c_void_p]),
+    "prc_cfar_training_cells": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "prc_cfar_os_workspace_bytes": (C.c_int, [C.POINTER(CfarOsDesc), C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_cfar_os": (C.c_int, [C.POINTER(CfarOsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "prc_decimate_iir": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(IirDesc), C.c_void_p, C.c_void_p]),
     "prc_channel_offset": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(IirDesc), C.c_int64,
                                      C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
@@ -317,7 +330,12 @@ def lib():
                                   f"{MIN_LIB_VERSION} (descriptor layout with struct_size): rebuild it with "
                                   f"`make -C passiveradar_amd/csrc`")
             for name, (res, args) in _SIGNATURES.items():
-                fn = getattr(handle, name)
+                try:
+                    fn = getattr(handle, name)
+                except AttributeError:
+                    # entry points added without a layout change keep PRC_VERSION (prc_cfar_os): the symbol is the check
+                    raise ImportError(f"{LIB_PATH} (prcore.h version {built}) has no {name}: it was built from an older "
+                                      f"source tree; rebuild it with `make -C passiveradar_amd/csrc`") from None
                 fn.restype = res
                 fn.argtypes = args
             _lib = handle

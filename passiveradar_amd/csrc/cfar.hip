@@ -6,32 +6,11 @@
 // (j + (fw-1)/2 - b) mod W]  (asymmetric for even fw -- reproduced, not "fixed").
 // One pass for the mean (block partials), one pass for the box sums from an LDS tile with wrap halo.
 #include "common.h"
+#include "cfar_mean.h"
 #include <vector>
 
 #define CF_TX 32
 #define CF_TY 8
-
-// The map comes in as magnitudes (float: CFAR_2D's own argument) or as the complex range-Doppler map itself (float2:
-// range_doppler_plot.py:56-57 calls CFAR_2D(np.abs(xambg), ...) -- |X| is then taken on the tile load, one read of the
-// complex map instead of an abs kernel's read + write and two reads of its result; np.abs of complex64 is hypotf).
-__device__ __forceinline__ float cfar_mag(float v) { return v; }
-__device__ __forceinline__ float cfar_mag(float2 v) { return hypotf(v.x, v.y); }
-
-template <typename TIn>
-__global__ void cfar_abs_partial_kernel(const TIn* __restrict__ X, int64_t n, float* __restrict__ partial) {
-    __shared__ float red[256];
-    const int f = blockIdx.y;
-    const TIn* x = X + (int64_t)f * n;
-    float s = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += fabsf(cfar_mag(x[i]));
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(int64_t)f * gridDim.x + blockIdx.x] = red[0];
-}
 
 template <typename TIn>
 __global__ __launch_bounds__(CF_TX * CF_TY) void cfar_kernel(const TIn* __restrict__ X, int H, int W, int fw,
@@ -180,7 +159,7 @@ static int cfar_run(const TIn* X, int32_t H, int32_t W, int32_t fw, int32_t gw, 
     PRC_REQUIRE(H > 0 && W > 0 && fw > 0 && gw >= 0 && nframes > 0, PRC_EINVAL, "prc_cfar2d: bad size");
     PRC_REQUIRE(fw * fw != gw * gw, PRC_EINVAL, "prc_cfar2d: fw^2 == gw^2 divides by zero (as in the reference)");
     hipStream_t stream = (hipStream_t)stream_;
-    const int np = 64;
+    const int np = CFAR_MEAN_PARTIALS;
     // scratch for the |X| partial sums: per host thread AND per (device, stream), grown on demand and kept.  Two
     // calls from one thread on different streams never share a buffer (the second call's partial-sum kernel could
     // otherwise overwrite what the first call's cfar_kernel has not read yet); calls on one stream are ordered by

@@ -381,6 +381,40 @@ def patch_list(lags, dopplers, frame=None, nframes=1, n=None):
     return rec
 
 
+def cfar_training_cells(fw, gw):
+    """training cells of CFAR_2D's (fw, gw) window: fw^2 - (e2 - e1)^2 (prc_cfar_training_cells; host arithmetic)"""
+    n = C.c_int32(0)
+    check(lib().prc_cfar_training_cells(int(fw), int(gw), C.byref(n)))
+    return int(n.value)
+
+
+def cfar_os_desc(H, W, fw, gw, rank=None, scale="reference", complex_input=False, thresh=None):
+    """prc_cfar_os_desc of include/prcore.h (rank None: the library's default, ceil(0.75 Nt))"""
+    if scale not in _lib.CFAR_SCALES:
+        raise ValueError(f"scale is one of {sorted(_lib.CFAR_SCALES)}, not {scale!r}")
+    if rank is not None and int(rank) < 1:
+        raise ValueError("rank counts from 1")
+    d = _lib.CfarOsDesc()
+    d.H, d.W, d.fw, d.gw = int(H), int(W), int(fw), int(gw)
+    d.rank = 0 if rank is None else int(rank)
+    d.scale, d.input = _lib.CFAR_SCALES[scale], int(bool(complex_input))
+    d.use_thresh, d.thresh = int(thresh is not None), float(thresh or 0.0)
+    return d
+
+
+def cfar_os_workspace_bytes(desc, nframes):
+    """device bytes prc_cfar_os needs in ``workspace`` (0 for the plain scale); validates the descriptor on the host"""
+    nb = C.c_size_t(0)
+    check(lib().prc_cfar_os_workspace_bytes(C.byref(desc), int(nframes), C.byref(nb)))
+    return int(nb.value)
+
+
+def cfar_os_execute(desc, X, out, noise, nframes, workspace, stream=None):
+    """order-statistic CFAR of a stack (device buffers or torch tensors; ``noise`` and, for the plain scale, ``workspace``
+    may be None)"""
+    check(lib().prc_cfar_os(C.byref(desc), _ptr(X), _ptr(out), _ptr(noise), int(nframes), _ptr(workspace), stream))
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

@@ -273,15 +273,18 @@ def render_frames(X, lut=None, limits=None, p_lo=35, p_hi=99, hi_scale=1.5, orie
 RENDER_SLAB_BYTES = 1 << 28     # render_maps: float64 persistence frames alive at a time (default slab)
 
 
-def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, **render_kw):
+def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, cfar="mean", cfar_rank=None, **render_kw):
     """range_doppler_plot.py:43-92 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per frame
     (CFAR_2D_abs; CFAR_2D for a real magnitude stack), persistence(CF, k, hold, decay) of the float64 CFAR maps for every
     k, then ``render_frames(**render_kw)``.  ``xambg`` is a torch device tensor [L, H, W] (result: a device tensor
     [L, W, H, 4], or [L, H, W, 4] for orient="stored") or numpy (H, W, L) as the script loads it (result: numpy; the
     chain runs through torch).  The float64 persistence frames exist ``slab`` frames at a time (default: as many as fit
-    RENDER_SLAB_BYTES); a slab reads the ``hold - 1`` CFAR frames before its first one.  Given ``limits`` are (L, 2)."""
+    RENDER_SLAB_BYTES); a slab reads the ``hold - 1`` CFAR frames before its first one.  Given ``limits`` are (L, 2).
+    ``cfar="os"`` puts CFAR_2D_OS (reference scale, rank ``cfar_rank``) in the cell average's place."""
     import torch
-    from .target_detection import CFAR_2D, CFAR_2D_abs
+    from .target_detection import _chain_cfar
+    if cfar not in ("mean", "os"):
+        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
     hold = int(hold)
     if slab is not None and int(slab) < 1:
         raise ValueError("slab is a number of frames >= 1")
@@ -291,7 +294,7 @@ def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, **render_kw):
             raise ValueError("render_maps takes (H, W, L) maps")
         _lib.require_gpu()
         x = np.ascontiguousarray(np.moveaxis(x, 2, 0), dtype=np.complex64 if np.iscomplexobj(x) else np.float32)
-        return render_maps(torch.from_numpy(x).cuda(), fw, gw, hold, decay, slab, **render_kw).cpu().numpy()
+        return render_maps(torch.from_numpy(x).cuda(), fw, gw, hold, decay, slab, cfar, cfar_rank, **render_kw).cpu().numpy()
     if xambg.dim() != 3:
         raise ValueError("render_maps takes a device stack [L, H, W]")
     L, H, W = xambg.shape
@@ -304,7 +307,7 @@ def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, **render_kw):
         limits = limits.to(device=xambg.device, dtype=torch.float64)
     if L == 0:
         return render_frames(torch.empty((0, H, W), dtype=torch.float64, device=xambg.device), limits=limits, **render_kw)
-    cf = CFAR_2D_abs(xambg, fw, gw) if xambg.is_complex() else CFAR_2D(xambg, fw, gw)
+    cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
     step = int(slab) if slab is not None else max(1, RENDER_SLAB_BYTES // (H * W * 8))
     outs = []
     for s0 in range(0, L, step):

@@ -3,7 +3,8 @@
 multitarget_kalman_tracker.py: ``get_measurements`` (:164-229) and ``multitarget_tracker`` (:455-537), plus
 ``track_maps``, that script's CFAR -> measure -> track chain (:44-63) in one device pass, and the single-target tracker
 of simple_kalman_tracker.py: ``simple_target_tracker`` (:626-681), plus ``simple_track_maps``, its CFAR -> track
-chain (:46-61)."""
+chain (:46-61).  Beyond the reference: ``CFAR_2D_OS``, the order-statistic CFAR on CFAR_2D's window (with
+``cfar_training_cells`` and ``os_cfar_threshold``), which the chains take with ``cfar="os"``, and ``refine_peaks``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,7 +14,8 @@ import numpy as np
 from . import _lib, engine
 from ._lib import check, lib
 
-__all__ = ["CFAR_2D", "CFAR_2D_abs", "get_measurements", "multitarget_tracker", "track_maps",
+__all__ = ["CFAR_2D", "CFAR_2D_abs", "CFAR_2D_OS", "cfar_training_cells", "os_cfar_threshold", "get_measurements",
+           "multitarget_tracker", "track_maps",
            "kalman_filter_dtype", "target_track_dtype", "simple_target_tracker", "simple_track_maps",
            "target_track_dtype_simple", "refine_peaks"]
 
@@ -75,6 +77,126 @@ def CFAR_2D_abs(xambg, fw, gw, thresh=None):
                                do.ptr, frames, None))
     out = do.download(x.shape, np.float32)
     return out > 0.5 if thresh is not None else out.astype(np.float64)
+
+
+# ---- order-statistic CFAR on CFAR_2D's window ----------------------------------------------------
+def cfar_training_cells(fw, gw):
+    """Training cells Nt of the (fw, gw) window: fw^2 - (e2 - e1)^2 with CFAR_2D's guard block [e1, e2)^2 -- 299 at (18, 4),
+    not the fw^2 - gw^2 of the reference's gain."""
+    return engine.cfar_training_cells(fw, gw)
+
+
+def os_cfar_threshold(pfa, ncells, rank, law="magnitude"):
+    """The multiplier of an order-statistic CFAR for a false-alarm probability: for square-law cells in exponential noise
+    Pfa(T) = prod_{i=0}^{rank-1} (N - i) / (N - i + T) (Rohling), solved for T by bisection in float64.
+    ``law="magnitude"`` (Rayleigh cells, what |xambg| is) returns sqrt(T), ``law="square"`` T itself.  The result is a
+    threshold for the ``plain`` scale of CFAR_2D_OS.  N = 299, rank = 225, Pfa = 1e-3: T = 5.055, sqrt(T) = 2.248."""
+    N, k, pfa = int(ncells), int(rank), float(pfa)
+    if law not in ("magnitude", "square"):
+        raise ValueError("law is 'magnitude' or 'square'")
+    if not 1 <= k <= N:
+        raise ValueError(f"rank = {k} outside 1 .. {N} cells")
+    if not 0.0 < pfa < 1.0:
+        raise ValueError("pfa is a probability inside (0, 1)")
+    m = N - np.arange(k, dtype=np.float64)
+
+    def log_pfa(T):
+        return float(np.sum(np.log(m) - np.log(m + T)))
+
+    target, lo, hi = np.log(pfa), 0.0, 1.0
+    while log_pfa(hi) > target:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if log_pfa(mid) > target:
+            lo = mid
+        else:
+            hi = mid
+    T = 0.5 * (lo + hi)
+    return float(np.sqrt(T)) if law == "magnitude" else float(T)
+
+
+def CFAR_2D_OS(X, fw, gw, thresh=None, *, rank=None, scale="reference", return_noise=False):
+    """Order-statistic CFAR on CFAR_2D's window: the noise estimate z of a cell is the ``rank``-th smallest (1-based,
+    default ceil(0.75 Nt)) of its Nt = cfar_training_cells(fw, gw) training cells, selected exactly, instead of their mean
+    -- a few strong cells in the window (a second target, the clutter ridge, a sidelobe) leave it untouched.
+    ``scale="reference"``: (X / mean|X|) / (z + 1e-10), CFAR_2D's own form, which the trackers and the render chain take
+    unchanged; ``scale="plain"``: X / z, the ratio os_cfar_threshold's multiplier applies to.
+    X is a 2-D map or a stack [nframes, H, W], NumPy or a torch device tensor, real or complex (|X| is taken on load, as
+    CFAR_2D_abs does).  Returns as CFAR_2D: float64 from NumPy (bool with ``thresh``), float32 / bool tensors on the caller's
+    device and stream for torch; with ``return_noise=True`` also the z map (float64 / float32)."""
+    dev = _lib.is_device_tensor(X)
+    if dev:
+        import torch
+        x = X.to(torch.complex64 if X.is_complex() else torch.float32).contiguous()
+        cplx, ndim = x.is_complex(), x.dim()
+    else:
+        x = np.asarray(X)
+        cplx, ndim = np.iscomplexobj(x), x.ndim
+        x = np.ascontiguousarray(x, dtype=np.complex64 if cplx else np.float32)
+    if ndim not in (2, 3):
+        raise ValueError("CFAR_2D_OS takes a 2-D map or a stack [nframes, H, W]")
+    frames = 1 if ndim == 2 else int(x.shape[0])
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    desc = engine.cfar_os_desc(H, W, fw, gw, rank, scale, cplx, thresh)
+    nws = engine.cfar_os_workspace_bytes(desc, max(frames, 1))     # every argument check, on the host
+    if dev:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        z = torch.empty_like(out) if return_noise else None
+        ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws else None
+        if frames:
+            with torch.cuda.device(x.device):          # launch on the tensor's device and torch's stream there
+                engine.cfar_os_execute(desc, x, out, z, frames, ws, _lib.torch_stream_ptr(x.device))
+        out = out.bool() if thresh is not None else out
+        return (out, z) if return_noise else out
+    _lib.require_gpu()
+    if frames == 0:
+        out = np.zeros(x.shape, dtype=bool if thresh is not None else np.float64)
+        return (out, np.zeros(x.shape, dtype=np.float64)) if return_noise else out
+    st = engine.staging()
+    nb = frames * H * W * 4
+    dx = st.get("cfar_xc" if cplx else "cfar_x", x.nbytes)
+    do = st.get("cfar_o", nb)
+    dz = st.get("cfar_z", nb) if return_noise else None
+    ws = st.get("cfar_ws", nws) if nws else None
+    dx.upload(x)
+    engine.cfar_os_execute(desc, dx, do, dz, frames, ws)
+    out = do.download(x.shape, np.float32)
+    out = out > 0.5 if thresh is not None else out.astype(np.float64)
+    return (out, dz.download(x.shape, np.float32).astype(np.float64)) if return_noise else out
+
+
+def _chain_cfar(x, fw, gw, cfar, cfar_rank):
+    """the CFAR stage of the device chains on a torch stack: "mean" = CFAR_2D / CFAR_2D_abs, "os" = CFAR_2D_OS"""
+    if cfar == "os":
+        return CFAR_2D_OS(x, fw, gw, rank=cfar_rank)
+    if cfar != "mean":
+        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
+    return CFAR_2D_abs(x, fw, gw) if x.is_complex() else CFAR_2D(x, fw, gw)
+
+
+def _chain_cfar_staged(x, fw, gw, cfar, cfar_rank):
+    """the same stage for a host stack [nframes, H, W] on buffers the chain owns (null stream): returns
+    (maps buffer, nframes, H, W, what must stay alive)"""
+    if cfar not in ("mean", "os"):
+        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
+    cplx = np.iscomplexobj(x)
+    xs = np.ascontiguousarray(x, dtype=np.complex64 if cplx else np.float32)
+    nframes, H, W = xs.shape
+    dx = _lib.DeviceBuffer(xs.nbytes)
+    dx.upload(xs)
+    do = _lib.DeviceBuffer(nframes * H * W * 4)
+    ws = None
+    if cfar == "os":
+        desc = engine.cfar_os_desc(H, W, fw, gw, cfar_rank, "reference", cplx)
+        ws = _lib.DeviceBuffer(engine.cfar_os_workspace_bytes(desc, nframes))
+        engine.cfar_os_execute(desc, dx, do, None, nframes, ws)
+    else:
+        fn = lib().prc_cfar2d_c64 if cplx else lib().prc_cfar2d
+        check(fn(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    return do, nframes, H, W, (dx, ws)
 
 
 # ---- multi-target tracker (target_detection.py:164-537) ---------------------------------------------------------------
@@ -276,32 +398,19 @@ def multitarget_tracker(data, frame_extent, N_TRACKS):
     return _records_to_history(m.run(), int(N_TRACKS))
 
 
-def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4):
+def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4, cfar="mean", cfar_rank=None):
     """multitarget_kalman_tracker.py:44-63 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per
     frame (CFAR_2D_abs; CFAR_2D for a real magnitude stack) -> get_measurements -> multitarget_tracker.  ``xambg`` is a
-    torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it."""
+    torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it.  ``cfar="os"`` puts CFAR_2D_OS
+    (reference scale, rank ``cfar_rank``, default ceil(0.75 Nt)) in the cell average's place."""
     if _lib.is_device_tensor(xambg):
-        import torch
-        cf = CFAR_2D_abs(xambg, fw, gw) if xambg.is_complex() else CFAR_2D(xambg, fw, gw)
+        cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
         if cf.dim() == 2:
             cf = cf.unsqueeze(0)
         return multitarget_tracker(cf, frame_extent, N_TRACKS)
     x = np.moveaxis(np.asarray(xambg), 2, 0)
     _lib.require_gpu()
-    if np.iscomplexobj(x):
-        xc = np.ascontiguousarray(x, dtype=np.complex64)
-        nframes, H, W = xc.shape
-        dx = _lib.DeviceBuffer(xc.nbytes)
-        dx.upload(xc)
-        do = _lib.DeviceBuffer(nframes * H * W * 4)
-        check(lib().prc_cfar2d_c64(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
-    else:
-        xf = np.ascontiguousarray(x, dtype=np.float32)
-        nframes, H, W = xf.shape
-        dx = _lib.DeviceBuffer(xf.nbytes)
-        dx.upload(xf)
-        do = _lib.DeviceBuffer(xf.nbytes)
-        check(lib().prc_cfar2d(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank)
     m = _Measured(do.ptr, nframes, H, W, frame_extent, int(N_TRACKS), lambda name, nb: _lib.DeviceBuffer(nb), None)
     return _records_to_history(m.run(), int(N_TRACKS))
 
@@ -404,31 +513,19 @@ def simple_target_tracker(data, rangeExtent, dopplerExtent, *, state=None):
     return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
 
 
-def simple_track_maps(xambg, rangeExtent, dopplerExtent, fw=18, gw=4):
+def simple_track_maps(xambg, rangeExtent, dopplerExtent, fw=18, gw=4, cfar="mean", cfar_rank=None):
     """simple_kalman_tracker.py:46-61 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per frame
     (CFAR_2D_abs; CFAR_2D for a real magnitude stack) -> simple_target_tracker on the float32 CFAR maps.  ``xambg`` is
-    a torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it."""
+    a torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it.  ``cfar="os"`` puts CFAR_2D_OS
+    (reference scale, rank ``cfar_rank``) in the cell average's place."""
     if _lib.is_device_tensor(xambg):
-        cf = CFAR_2D_abs(xambg, fw, gw) if xambg.is_complex() else CFAR_2D(xambg, fw, gw)
+        cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
         if cf.dim() == 2:
             cf = cf.unsqueeze(0)
         return simple_target_tracker(cf, rangeExtent, dopplerExtent)
     x = np.moveaxis(np.asarray(xambg), 2, 0)
     _lib.require_gpu()
-    if np.iscomplexobj(x):
-        xc = np.ascontiguousarray(x, dtype=np.complex64)
-        nframes, H, W = xc.shape
-        dx = _lib.DeviceBuffer(xc.nbytes)
-        dx.upload(xc)
-        do = _lib.DeviceBuffer(nframes * H * W * 4)
-        check(lib().prc_cfar2d_c64(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
-    else:
-        xf = np.ascontiguousarray(x, dtype=np.float32)
-        nframes, H, W = xf.shape
-        dx = _lib.DeviceBuffer(xf.nbytes)
-        dx.upload(xf)
-        do = _lib.DeviceBuffer(xf.nbytes)
-        check(lib().prc_cfar2d(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
+    do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank)
     rec = _strack_run(do.ptr, nframes, H, W, _lib.REAL_F32, rangeExtent, dopplerExtent, None,
                       lambda nb: _lib.DeviceBuffer(nb), None)
     return _strack_records_to_history(rec, rangeExtent, dopplerExtent)

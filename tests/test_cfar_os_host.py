@@ -1,0 +1,139 @@
+"""Order-statistic CFAR without a GPU: the oracle's window against oracle/np_oracle.py::CFAR_2D's box, the training-cell
+count, the ranks at both ends, the false-alarm threshold (closed form and a Monte-Carlo run of the oracle) and the argument
+checks, which the library makes on the host."""
+import numpy as np
+import pytest
+
+import cfar_os_oracle as OS
+from oracle import np_oracle as O
+
+WINDOWS = [(3, 1), (9, 2), (18, 4), (33, 6), (8, 2)]
+
+
+@pytest.mark.parametrize("fw,gw", WINDOWS)
+@pytest.mark.parametrize("shape", [(5, 7), (20, 31)])
+def test_training_set_is_the_box_of_cfar_2d(fw, gw, shape):
+    """the mean-scaled sum over the oracle's training set == the box CFAR_2D divides by (multiple wrap included)"""
+    X = np.abs(np.random.default_rng(3).standard_normal(shape)) + 0.1
+    box = OS.training_stack(X, fw, gw).sum(0) / (fw ** 2 - gw ** 2)
+    ref = (X / np.mean(np.abs(X))) / O.CFAR_2D(X, fw, gw) - 1e-10
+    assert np.abs(box - ref).max() < 1e-12
+
+
+def test_training_cells():
+    from passiveradar_amd.target_detection import cfar_training_cells
+    assert cfar_training_cells(18, 4) == 299 == OS.training_cells(18, 4)
+    assert cfar_training_cells(3, 1) == 5 == OS.training_cells(3, 1)
+    assert OS.default_rank(18, 4) == 225
+    for fw, gw in WINDOWS + [(1, 0), (2, 7), (4, 4)]:
+        assert cfar_training_cells(fw, gw) == OS.training_cells(fw, gw) == len(OS.taps(fw, gw)), (fw, gw)
+    with pytest.raises(ValueError):
+        cfar_training_cells(0, 0)
+
+
+@pytest.mark.parametrize("fw,gw", [(3, 1), (18, 4)])
+def test_rank_ends_are_the_window_extremes(fw, gw):
+    """rank 1 is the window minimum and rank Nt its maximum, computed cell by cell without the stack"""
+    rng = np.random.default_rng(4)
+    X = rng.standard_normal((7, 9)).astype(np.float32)
+    H, W = X.shape
+    c, e1, e2 = OS.window(fw, gw)
+    lo, hi = np.full(X.shape, np.inf, np.float32), np.full(X.shape, -np.inf, np.float32)
+    for i in range(H):
+        for j in range(W):
+            for a in range(fw):
+                for b in range(fw):
+                    if e1 <= a < e2 and e1 <= b < e2:
+                        continue
+                    v = X[(i + c - a) % H, (j + c - b) % W]
+                    lo[i, j], hi[i, j] = min(lo[i, j], v), max(hi[i, j], v)
+    assert np.array_equal(OS.noise(X, fw, gw, 1), lo)
+    assert np.array_equal(OS.noise(X, fw, gw, OS.training_cells(fw, gw)), hi)
+
+
+def test_threshold_closed_form():
+    from passiveradar_amd.target_detection import os_cfar_threshold
+    T = os_cfar_threshold(1e-3, 299, 225, law="square")
+    a = os_cfar_threshold(1e-3, 299, 225)
+    assert abs(T - 5.055) < 1e-3 and abs(a - 2.248) < 1e-3
+    assert abs(a - np.sqrt(T)) < 1e-12
+    assert abs(OS.pfa(T, 299, 225) - 1e-3) < 1e-12
+    # rank 1 of 1 cell: Pfa = 1 / (1 + T)
+    assert abs(os_cfar_threshold(0.25, 1, 1, law="square") - 3.0) < 1e-9
+    for bad in ((0.0, 299, 225), (1.0, 299, 225), (1e-3, 299, 300), (1e-3, 299, 0)):
+        with pytest.raises(ValueError):
+            os_cfar_threshold(*bad)
+    with pytest.raises(ValueError):
+        os_cfar_threshold(1e-3, 299, 225, law="cubic")
+
+
+def test_threshold_monte_carlo_on_the_oracle():
+    """40 frames of 64 x 96 complex Gaussian noise (245 760 cells): at the Pfa = 1e-3 threshold the plain ratio of the oracle
+    crosses at a rate inside [0.5, 2] 1e-3.  The cells of a frame share training cells, so the count is not binomial; the
+    bracket is the issue's."""
+    from passiveradar_amd.target_detection import os_cfar_threshold
+    alpha = os_cfar_threshold(1e-3, 299, 225)
+    rng = np.random.default_rng(2024)
+    hits = cells = 0
+    for _ in range(40):
+        X = np.abs(rng.standard_normal((64, 96)) + 1j * rng.standard_normal((64, 96))).astype(np.float32)
+        hits += int(OS.CFAR_2D_OS(X, 18, 4, thresh=alpha, scale="plain").sum())
+        cells += X.size
+    rate = hits / cells
+    print(f"alpha {alpha:.4f}: {hits} crossings in {cells} cells, rate {rate:.3e}")
+    assert cells == 245760 and 0.5e-3 <= rate <= 2e-3, rate
+
+
+def test_argument_errors_need_no_device():
+    """rank > Nt, Nt == 0, a bad scale, a rank below 1 and a 1-D map are ValueError before anything touches a device"""
+    from passiveradar_amd.target_detection import CFAR_2D_OS
+    X = np.ones((8, 9), np.float32)
+    with pytest.raises(ValueError, match="rank"):
+        CFAR_2D_OS(X, 18, 4, rank=300)
+    with pytest.raises(ValueError, match="no training cell"):
+        CFAR_2D_OS(X, 1, 0)
+    with pytest.raises(ValueError):
+        CFAR_2D_OS(X, 18, 4, scale="decibel")
+    with pytest.raises(ValueError):
+        CFAR_2D_OS(X, 18, 4, rank=0)
+    with pytest.raises(ValueError):
+        CFAR_2D_OS(X, 0, 0)
+    with pytest.raises(ValueError):
+        CFAR_2D_OS(np.ones(8, np.float32), 18, 4)
+    with pytest.raises(NotImplementedError):
+        CFAR_2D_OS(X, 200, 4)
+    with pytest.raises(ValueError):
+        OS.noise(X, 18, 4, 300)
+    with pytest.raises(ValueError):
+        OS.noise(X, 1, 0)
+
+
+def test_chain_keyword_is_checked():
+    from passiveradar_amd.plotting_tools import render_maps
+    from passiveradar_amd.target_detection import _chain_cfar_staged
+    with pytest.raises(ValueError, match="cfar"):
+        _chain_cfar_staged(np.ones((2, 8, 9), np.float32), 18, 4, "median", None)
+    with pytest.raises(ValueError, match="cfar"):
+        render_maps(np.ones((4, 3, 2)), cfar="median")
+
+
+def test_descriptor_matches_the_header(tmp_path):
+    """sizeof / offsetof of prc_cfar_os_desc as gcc lays it out == the ctypes mirror"""
+    import ctypes
+    import shutil
+    import subprocess
+    from conftest import REPO
+    from passiveradar_amd import _lib
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "include/prcore.h"\nint main(void) {\n'
+                   '  printf("%zu %zu %zu %zu %u %d %d\\n", sizeof(prc_cfar_os_desc), offsetof(prc_cfar_os_desc, rank),\n'
+                   '         offsetof(prc_cfar_os_desc, input), offsetof(prc_cfar_os_desc, thresh), PRC_CFAR_OS_DESC_SIZE_MIN,\n'
+                   '         (int)PRC_CFAR_SCALE_REFERENCE, (int)PRC_CFAR_SCALE_PLAIN); return 0; }\n')
+    exe = tmp_path / "sz"
+    subprocess.check_call(["gcc", "-I", REPO, str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    D = _lib.CfarOsDesc
+    assert got == [ctypes.sizeof(D), D.rank.offset, D.input.offset, D.thresh.offset, ctypes.sizeof(D),
+                   _lib.CFAR_SCALE_REFERENCE, _lib.CFAR_SCALE_PLAIN]
