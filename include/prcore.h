@@ -52,8 +52,10 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, second edition (additions only, no layout of 680 changed, so the number stays: a host checks for the new
-                             entry points by symbol): prc_cfar_os_desc, prc_cfar_training_cells, prc_cfar_os_workspace_bytes, prc_cfar_os
+#define PRC_VERSION 680   /* 680, third edition (additions only, no layout of 680 changed, so the number stays: a host checks for the new
+                             entry points by symbol): prc_eca_workspace_bytes, prc_eca_execute, prc_eca_set_profiling, prc_eca_get_profile
+                             (ECA_Filter, the joint multi-Doppler least-squares canceller, on device);
+                             680, second edition (the same way): prc_cfar_os_desc, prc_cfar_training_cells, prc_cfar_os_workspace_bytes, prc_cfar_os
                              (order-statistic CFAR on CFAR_2D's window, on device);
                              680: prc_patch_desc, prc_patch, prc_patch_peak, prc_xambg_patch_workspace_bytes, prc_xambg_patch, prc_xambg_patch_peaks
                              (exact, un-decimated cross-ambiguity patches and sub-cell peak refinement on device);
@@ -323,6 +325,39 @@ int prc_ls_svd_execute(const void* ref, const void* srv, int64_t n, int64_t stri
  * taps) and apply (the FIR), and the number of sweeps launched. */
 int prc_ls_svd_set_profiling(int32_t enable);
 int prc_ls_svd_get_profile(double* ms /* [4] */, int32_t* sweeps);
+
+/* ---- ECA_Filter: joint multi-Doppler least squares (extensive cancellation algorithm) ---- */
+/* nblocks independent cancellers that solve for the taps of ALL nbins Doppler bins at once, where prc_ls_execute with the same
+ * bins solves one bin after another on the previous bin's output.  T = filter_len + peek taps per bin.  Regressors
+ * r_a = roll(ref ramp_a, -peek), ramp_a the float32-phase ramp of prc_frequency_shift at doppler_bins_host[a] (Hz) and
+ * sample_rate, r_a = roll(ref, -peek) for a bin of 0.  In LS_Filter_Toeplitz's convention (linear lags, zero outside [0, n)):
+ *     R_k[a][c] = sum_m r_c[m] conj(r_a[m-k]),  y_k[a] = sum_m srv[m] conj(r_a[m-k]),  sum_j R_{i-j} x_j = y_i  (R_-k = R_k^H),
+ * `reg` >= 0 added to the diagonal of R_0, and out = srv - sum_a (r_a * w_a)[0:n] with w_a[j] = x_j[a], a linear FIR with zero
+ * history (complex64).  With nbins = 1 this is prc_ls_execute with that one bin (non-circular).  Products and sums are float64
+ * in a fixed order (no floating-point atomics), the solve is a block Levinson recursion in float64, the FIR keeps its taps in
+ * float64.  Block b reads ref and srv at b*stride and writes out at b*out_stride.
+ * taps_out: optional complex128 [nblocks][nbins][T]; info_out: optional int32 [nblocks], 0, or 1 for a block whose recursion
+ * broke down: a pivot of a prediction-error block not above 2^-40 of R_0's diagonal, or anything non-finite.  Such a block
+ * gets zero taps and out = srv bit for bit; nothing non-finite is stored.  Duplicate bins and an all-zero reference, both
+ * with reg = 0, are the cases that reach this; bins closer than 1 / (n / sample_rate) make G ill-conditioned and are what
+ * `reg` is for.
+ * workspace: prc_eca_workspace_bytes(...) bytes of device memory, 16-byte aligned, owned by the caller and not shared by calls
+ * in flight; nothing in it needs initialising (per block about 80 nbins^2 T bytes plus the correlation partials, at most
+ * 64 x 16 nbins (nbins + 1) T bytes).
+ * The call neither allocates nor synchronises, has a fixed number of launches and reads nothing back: it can be captured
+ * into a graph.  Results are bit-identical from run to run and do not depend on which other blocks share the call.
+ * Limits: 1 <= T < n, 1 <= nbins <= 8, nbins * T <= 4096, stride and out_stride >= n.  Anything else, a null ref / srv / out /
+ * doppler_bins_host / workspace, a misaligned workspace, a negative or non-finite reg or a zero sample_rate: PRC_EINVAL. */
+int prc_eca_workspace_bytes(int64_t n, int32_t filter_len, int32_t peek, int32_t nbins, int32_t nblocks, size_t* bytes);
+int prc_eca_execute(const void* ref, const void* srv, int64_t n, int64_t stride, int32_t filter_len, int32_t peek,
+                    double sample_rate, const double* doppler_bins_host, int32_t nbins, double reg, int32_t nblocks,
+                    void* out, int64_t out_stride, void* taps_out /* c128 [nblocks][nbins][T] or NULL */,
+                    int32_t* info_out /* [nblocks] or NULL */, void* workspace, void* stream);
+/* Stage timing for tools/eca_bench.py, process-wide: while enabled, every prc_eca_execute records events around its stages and
+ * waits for its last kernel; get_profile returns the last call's milliseconds for correlate (float64 correlations and their
+ * reduction), solve (block Levinson) and apply (the FIR of every bin). */
+int prc_eca_set_profiling(int32_t enable);
+int prc_eca_get_profile(double* ms /* [3] */);
 
 /* ---- GAL_JPE (clutter_removal.py:251-365) --------------------------------------------- */
 /* nstreams independent gradient-adaptive-lattice joint-process estimators: lattice_len reflection coefficients k, then a

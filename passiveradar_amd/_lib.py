@@ -217,6 +217,12 @@ _SIGNATURES = {
                                      C.c_void_p]),
     "prc_ls_svd_set_profiling": (C.c_int, [C.c_int32]),
     "prc_ls_svd_get_profile": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "prc_eca_workspace_bytes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_eca_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                  C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "prc_eca_set_profiling": (C.c_int, [C.c_int32]),
+    "prc_eca_get_profile": (C.c_int, [C.POINTER(C.c_double)]),
     "prc_frontend_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(FrontendDesc)]),
     "prc_frontend_plan_destroy": (C.c_int, [C.c_void_p]),
     "prc_frontend_out_len": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -5,6 +5,7 @@ LS_Filter_Multiple (:162-187), NLMS_filter (:189-249), and GAL_JPE (:251-365), a
 mismatched inputs; the arithmetic runs in libprcore.so (complex64 streams, complex128 Levinson solve
 on device).  LS_Filter_SVD is the truncated-SVD form through the float64 Gram matrix of the circulant
 data matrix (csrc/ls_svd.hip); it adds a relative cut ``rcond`` to the reference's absolute one.
+ECA_Filter is not in the reference: LS_Filter_Multiple's bins solved jointly instead of one after another (csrc/eca.hip).
 """
 from __future__ import annotations
 
@@ -12,7 +13,7 @@ import numpy as np
 
 from . import _lib, engine
 
-__all__ = ["LS_Filter", "LS_Filter_SVD", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "NLMS_filter", "GAL_JPE",
+__all__ = ["LS_Filter", "LS_Filter_SVD", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "ECA_Filter", "NLMS_filter", "GAL_JPE",
            "set_default_ls_method"]
 
 _LS_METHOD = {"m": 0}     # 0 auto | 1 time-domain kernels | 2 FFT kernels (tests flip it)
@@ -116,6 +117,47 @@ def LS_Filter_SVD(refChannel, srvChannel, filterLen, peek=10, return_filter=Fals
     if return_singular_values:
         res.append(d_sv.download((T,), np.float64))
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def ECA_Filter(refChannel, srvChannel, filterLen, sampleRate, dopplerBins=[0], peek=10, reg=0.0, return_filter=False):
+    """Joint multi-Doppler least-squares canceller (the extensive cancellation algorithm of Colone et al.): the taps of every
+    bin of ``dopplerBins`` from ONE least-squares problem, where LS_Filter_Multiple cancels one bin after another on the
+    previous bin's output -- one Gauss-Seidel sweep over subspaces that are far from orthogonal (a 1 Hz shift over a 0.5 s
+    block correlates at 0.64 with its neighbour), which leaves some 20 dB of slowly fluctuating clutter behind.
+
+    Regressors r_a = roll(frequency_shift(ref, f_a, sampleRate), -peek), normal equations and output in
+    LS_Filter_Toeplitz's convention (csrc/eca.hip); with one bin this is LS_Filter_Multiple(..., [f]).  ``reg`` >= 0 is added
+    to the diagonal of the normal equations.  Bins closer than 1 / (block duration) make them ill-conditioned: that is what
+    ``reg`` is for; duplicate bins or an all-zero reference with reg = 0 break the recursion down and raise PrcoreError.
+
+    Returns complex128 values of the device's complex64 stream, like LS_Filter_Multiple; with ``return_filter`` also the
+    taps, complex128 (len(dopplerBins), filterLen + peek).  Empty ``dopplerBins`` return srvChannel."""
+    _check_same(refChannel, srvChannel)
+    bins = [float(b) for b in dopplerBins]
+    if not bins:
+        return srvChannel
+    ref = np.ascontiguousarray(refChannel, dtype=np.complex64).reshape(-1)
+    srv = np.ascontiguousarray(srvChannel, dtype=np.complex64).reshape(-1)
+    n, B = ref.shape[0], len(bins)
+    T = int(filterLen) + int(peek)
+    wsb = engine.eca_workspace_bytes(n, filterLen, peek, B, 1)      # the size limits: ValueError
+    st = engine.staging()
+    d_ref = st.get("eca_ref", 8 * n)
+    d_srv = st.get("eca_srv", 8 * n)
+    d_out = st.get("eca_out", 8 * n)
+    d_taps = st.get("eca_taps", 16 * B * T)
+    d_info = st.get("eca_info", 4)
+    d_ws = st.get("eca_ws", wsb)
+    d_ref.upload(ref)
+    d_srv.upload(srv)
+    engine.eca_execute(d_ref, d_srv, d_out, n, filterLen, peek, float(sampleRate), bins, float(reg), 1, n, n, d_taps, d_info, d_ws)
+    if int(d_info.download((1,), np.int32)[0]):
+        raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, "ECA_Filter: the block Levinson recursion broke down (singular normal "
+                               "equations: duplicate bins or a silent reference); pass reg > 0")
+    out = d_out.download((n,), np.complex64).reshape(np.shape(srvChannel)).astype(np.complex128)
+    if return_filter:
+        return out, d_taps.download((B, T), np.complex128)
+    return out
 
 
 def NLMS_filter(refChannel, srvChannel, filterLen, mu, peek=10, initialTaps=None, returnFilter=False):

@@ -333,6 +333,37 @@ def ls_svd_get_profile():
     return tuple(ms), k.value
 
 
+def eca_workspace_bytes(n, filter_len, peek=10, nbins=1, nblocks=1):
+    """device bytes prc_eca_execute needs for ``nblocks`` blocks of ``n`` samples, ``nbins`` bins and filter_len + peek taps each"""
+    nb = C.c_size_t(0)
+    check(lib().prc_eca_workspace_bytes(int(n), int(filter_len), int(peek), int(nbins), int(nblocks), C.byref(nb)))
+    return int(nb.value)
+
+
+def eca_execute(ref, srv, out, n, filter_len, peek=10, sample_rate=1.0, doppler_bins=(0,), reg=0.0, nblocks=1, stride=None,
+                out_stride=None, taps_out=None, info_out=None, workspace=None, stream=None):
+    """ECA_Filter over ``nblocks`` independent blocks (device buffers or torch tensors): the taps of every Doppler bin from one
+    least-squares problem (include/prcore.h).  ``taps_out`` complex128 [nblocks][nbins][T], ``info_out`` int32 [nblocks] (1: the
+    block's recursion broke down, its taps are zero and out = srv); ``workspace``: eca_workspace_bytes(...) device bytes.
+    Neither allocates nor synchronises."""
+    bins = (C.c_double * max(len(doppler_bins), 1))(*[float(b) for b in doppler_bins])
+    check(lib().prc_eca_execute(_ptr(ref), _ptr(srv), int(n), int(n if stride is None else stride), int(filter_len), int(peek),
+                                float(sample_rate), bins, len(doppler_bins), float(reg), int(nblocks), _ptr(out),
+                                int(n if out_stride is None else out_stride), _ptr(taps_out), _ptr(info_out), _ptr(workspace),
+                                stream))
+
+
+def eca_set_profiling(enable=True):
+    check(lib().prc_eca_set_profiling(int(bool(enable))))
+
+
+def eca_get_profile():
+    """(ms_correlate, ms_solve, ms_apply) of the last eca_execute under set_profiling"""
+    ms = (C.c_double * 3)()
+    check(lib().prc_eca_get_profile(ms))
+    return tuple(ms)
+
+
 def patch_desc(n, nlags, ndoppler, sample_rate, doppler_step, wrap=True, nframes=1, frame_stride=None):
     """prc_patch_desc of include/prcore.h"""
     d = _lib.PatchDesc()

@@ -378,7 +378,7 @@ class HipBackend:
     """
 
     LS_HALO = 2        # spare blocks in every LS plan (the two halo chunks of a sharded stream)
-    CLUTTER_MODES = ("ls", "ls_direct", "ls_svd", "nlms", "gal", None)
+    CLUTTER_MODES = ("ls", "ls_direct", "ls_svd", "eca", "nlms", "gal", None)
 
     def __init__(self, cpi_samples, num_range_cells, num_doppler_cells, IF_sample_rate,
                  doppler_bins=(0, 1, -1, 2, -2), window=("kaiser", 5.0), clutter="ls",
@@ -391,7 +391,9 @@ class HipBackend:
         (clutter_removal.py:251-365) with ``gal_lattice`` reflection coefficients, a delay line of R taps and peek 10 (the
         lengths "nlms" uses) and steps ``gal_mu`` = (mu1, mu2), "ls_svd" = LS_Filter_SVD (clutter_removal.py:58-107:
         the circular data matrix of "ls_direct", truncated SVD with the relative cut ``ls_rcond``, None = its default; one
-        block per hop chunk, every chunk in one call, which synchronises the stream once per Jacobi sweep), None = no
+        block per hop chunk, every chunk in one call, which synchronises the stream once per Jacobi sweep), "eca" =
+        ECA_Filter (the taps of every bin of ``doppler_bins`` from one least-squares problem per hop chunk, R + 10 taps per
+        bin, ``ls_reg`` on the diagonal of its normal equations; every chunk in one call), None = no
         canceller.  The GAL defaults: (1e-3, 1e-2) are the
         ballpark step sizes of the reference's docstring, and 8 reflection coefficients (at most 64 take the faster row
         form of the kernel) are enough to whiten AR-like FM / OFDM spectra.  GAL restarts on every hop chunk, as the
@@ -424,6 +426,7 @@ class HipBackend:
         self._gal_ws = None
         self.ls_rcond = None if ls_rcond is None else float(ls_rcond)
         self._svd_ws = None
+        self._eca_ws = None
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         # LS launches of batch/nsub chunks.  Measured on MI355X (config 2, two LS chains in flight): 256-chunk launches
         # (nsub = 1) 20.45 k frames/s, 128-chunk launches (nsub = 2) 19.56 k -- the latency-bound Durbin / solve kernels
@@ -572,6 +575,17 @@ class HipBackend:
             if not bool(info[:, 2].all()):
                 from . import _lib
                 raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, "HipBackend: LS_Filter_SVD did not converge on every chunk")
+        elif self.clutter == "eca":
+            wsb = self.engine.eca_workspace_bytes(C, self.R, 10, len(self.bins), nb)
+            if self._eca_ws is None or self._eca_ws.numel() < wsb:
+                self._eca_ws = self.torch.empty(wsb, dtype=self.torch.uint8, device=self.device)
+            info = self.torch.empty(nb, dtype=self.torch.int32, device=self.device)
+            self.engine.eca_execute(ref_pad[off:], srv_pad[off:], out[off:], C, self.R, 10, self.fs, self.bins, self.ls_reg, nb,
+                                    C, C, None, info, self._eca_ws, stream)
+            if bool(info.any()):
+                from . import _lib
+                raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, "HipBackend: ECA_Filter broke down on a chunk (singular normal "
+                                       "equations: duplicate bins or a silent reference with ls_reg = 0)")
         elif self.clutter == "gal":
             wsb = self.engine.gal_workspace_bytes(self.R, nb)
             ws = None
