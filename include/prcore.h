@@ -35,7 +35,7 @@
  *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
- *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os).
+ *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -52,7 +52,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, third edition (additions only, no layout of 680 changed, so the number stays: a host checks for the new
+#define PRC_VERSION 680   /* 680, fourth edition (additions only, the number stays as for the editions below): prc_plots_desc, prc_plot_info,
+                             prc_plots_workspace_bytes, prc_plots (plot extraction: CFAR detections clustered into plots, on device);
+                             680, third edition (additions only, no layout of 680 changed, so the number stays: a host checks for the new
                              entry points by symbol): prc_eca_workspace_bytes, prc_eca_execute, prc_eca_set_profiling, prc_eca_get_profile
                              (ECA_Filter, the joint multi-Doppler least-squares canceller, on device);
                              680, second edition (the same way): prc_cfar_os_desc, prc_cfar_training_cells, prc_cfar_os_workspace_bytes, prc_cfar_os
@@ -601,6 +603,66 @@ int prc_track_measure(prc_track_plan* plan, const float* frames, int32_t nframes
  * start free (initialize_track(None)) at every call. */
 int prc_track_run(prc_track_plan* plan, const int32_t* counts, const prc_track_cand* cands, int32_t nframes,
                   prc_track_record* records, void* stream);
+
+/* ---- plot extraction: connected clusters of CFAR detections, one measurement per cluster: DESIGN.md section 20 ------ */
+/* Beyond the reference (which has no plot extractor): the stage between a CFAR statistic and prc_track_run.
+ * stat: DEVICE float32 [nframes][H][W] (H Doppler rows, W range columns: what prc_cfar2d / prc_cfar_os write).  weight: NULL
+ * (the weights are stat itself) or DEVICE [nframes][H][W], float32 (weight_input = 0) or complex64 (1: |.| = hypotf on load,
+ * evaluated through float64 -- exact squares, a rounded sum, a rounded root -- and rounded to float32).
+ * Detection: storage cell i = h W + w detects iff stat[i] > thresh (float32 compare: NaN never detects, +Inf does) and it lies
+ *   outside the excluded zones, get_measurements' masks with their widths as parameters: w < range_guard or
+ *   w >= W - range_guard; Doppler column c = H-1-h inside [H/2 - doppler_guard, H/2 + doppler_guard).  The reference's widths
+ *   are 8 and 4; 0 switches a zone off.
+ * Plot: a connected component of detecting cells under `connectivity` 4 or 8 in (h, w); neither axis wraps.
+ * Per plot, g = the weight of a cell as float64, members taken in ascending storage index: ncells; the inclusive box h0, h1,
+ *   w0, w1; mass M = sum g, hbar = (sum g h) / M, wbar = (sum g w) / M, every add and divide rounded on its own (g h is exact);
+ *   if M is not finite or not > 0, hbar, wbar are the peak cell's h, w.  Peak: the member with the largest stat, ties to the
+ *   smallest storage index; strength = that stat as float64, peak = its storage index, index = w_p H + (H-1-h_p) (the flat
+ *   index of prc_track_cand).  Coordinates, get_measurements' axes evaluated at the centroid (an integer centroid gives
+ *   numpy's arange * step + start): range = wbar ((0 - R) / (W-1)) + R, doppler = ((H-1) - hbar) (2 D / (H-1)) + (-D),
+ *   R = range_extent, D = doppler_extent.
+ * Order of a frame's plots: descending strength, ties by descending index (prc_track_measure's key).
+ * Capacities: ncells_out[f] is always the frame's true detection count.  A frame with more than max_cells detections gets
+ *   counts[f] = 0 and nothing else written; the other frames of the call are unaffected.  Otherwise counts[f] = the true
+ *   number of plots (it may exceed capacity) and the first min(counts[f], capacity) plots in the order above are written to
+ *   cands[f][.] (and info[f][.]); slots beyond that are not touched.  cands is what prc_track_run takes from a track plan of
+ *   the same capacity.
+ * Storage: one 1024-thread workgroup per frame keeps three lists of C = 2^ceil(log2 min(max_cells, H W)) entries, 20 C bytes
+ *   (two of 8-byte keys, one of 4-byte positions).  Up to PRC_PLOTS_LDS_CELLS = 4096 cells they sit in LDS: 20 * 4096 = 80 KiB
+ *   of the 160 KiB a CDNA4 workgroup can address (8192 cells would need all 160 KiB and leave nothing for the counters).
+ *   Above, the same code runs on frame f's slice [20 C f, 20 C (f+1)) of `workspace` (prc_plots_workspace_bytes bytes, 8-byte
+ *   aligned, not shared by calls in flight; 0 bytes and NULL allowed on the LDS path): slower, same bytes out.
+ * Results are a pure function of the inputs (integer atomics only, no float atomics): the same bytes on every call and on
+ * both storage paths.  One kernel on `stream`; the call allocates, frees, copies and synchronises nothing (it can be
+ * captured).  Memory: frame f of stat / weight is read only inside its H W elements; element alignment suffices.
+ * PRC_ESHAPE: H or W < 2, H W > 2^31 - 1.  PRC_EINVAL: a bad descriptor header, connectivity not 4 or 8, a negative guard,
+ * max_cells or capacity < 1, a NaN thresh, an extent that is not finite, weight_input not 0 or 1 with a weight, nframes < 0,
+ * a null stat / counts / ncells_out / cands, a missing or misaligned workspace where one is needed.  Every check is host
+ * arithmetic and needs no device; nframes == 0 is a no-op. */
+#define PRC_PLOTS_LDS_CELLS 4096
+typedef struct prc_plots_desc {
+    uint32_t struct_size;  /* sizeof(prc_plots_desc) as the host compiled it (see Conventions)       */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int32_t H, W;          /* Doppler rows, range columns of a frame (>= 2 each)                      */
+    int32_t connectivity;  /* 4 or 8                                                                  */
+    int32_t range_guard, doppler_guard;   /* >= 0; the reference's masks are 8 and 4                  */
+    int32_t max_cells;     /* detections held per frame (>= 1)                                        */
+    int32_t capacity;      /* plots stored per frame (>= 1)                                           */
+    int32_t weight_input;  /* 0 = float32, 1 = complex64; ignored when weight == NULL                 */
+    float thresh;          /* NaN: PRC_EINVAL                                                         */
+    double doppler_extent; /* frame_extent[0] (Hz)                                                    */
+    double range_extent;   /* frame_extent[1] (km)                                                    */
+} prc_plots_desc;
+#define PRC_PLOTS_DESC_SIZE_MIN 64u
+typedef struct prc_plot_info {
+    double mass, hbar, wbar;
+    int32_t ncells, h0, h1, w0, w1, peak;
+} prc_plot_info;
+#define PRC_PLOT_INFO_SIZE 48u
+int prc_plots_workspace_bytes(const prc_plots_desc* desc, int32_t nframes, size_t* bytes);
+int prc_plots(const prc_plots_desc* desc, const float* stat, const void* weight /* or NULL */, int32_t nframes,
+              int32_t* counts, int32_t* ncells_out, prc_track_cand* cands /* [nframes][capacity] */,
+              prc_plot_info* info /* or NULL, [nframes][capacity] */, void* workspace, void* stream);
 
 /* ---- single-target tracker: target_detection.py:530-681 (simple_target_tracker) ------------------------------------ */
 /* Frames are [nframes][H][W] (H Doppler rows, W range columns), float32 (the CFAR output) or float64.  The result is the

@@ -152,6 +152,23 @@ class CfarOsDesc(_Desc):
 CFAR_SCALE_REFERENCE, CFAR_SCALE_PLAIN = 0, 1      # prc_cfar_scale
 CFAR_SCALES = {"reference": CFAR_SCALE_REFERENCE, "plain": CFAR_SCALE_PLAIN}
 
+class PlotsDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("H", C.c_int32), ("W", C.c_int32), ("connectivity", C.c_int32), ("range_guard", C.c_int32),
+                ("doppler_guard", C.c_int32), ("max_cells", C.c_int32), ("capacity", C.c_int32), ("weight_input", C.c_int32),
+                ("thresh", C.c_float), ("doppler_extent", C.c_double), ("range_extent", C.c_double)]
+
+
+class PlotInfo(C.Structure):
+    _fields_ = [("mass", C.c_double), ("hbar", C.c_double), ("wbar", C.c_double), ("ncells", C.c_int32), ("h0", C.c_int32),
+                ("h1", C.c_int32), ("w0", C.c_int32), ("w1", C.c_int32), ("peak", C.c_int32)]
+
+
+# NumPy view of prc_plot_info (same layout as the ctypes mirror)
+PLOT_INFO_DTYPE = np.dtype([("mass", "<f8"), ("hbar", "<f8"), ("wbar", "<f8"), ("ncells", "<i4"), ("h0", "<i4"), ("h1", "<i4"),
+                            ("w0", "<i4"), ("w1", "<i4"), ("peak", "<i4")])
+PLOTS_LDS_CELLS = 4096       # PRC_PLOTS_LDS_CELLS: detections per frame prc_plots holds in LDS (above: the caller's workspace)
+
 FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
 
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
@@ -253,6 +270,9 @@ _SIGNATURES = {
     "prc_track_plan_destroy": (C.c_int, [C.c_void_p]),
     "prc_track_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_track_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "prc_plots_workspace_bytes": (C.c_int, [C.POINTER(PlotsDesc), C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_plots": (C.c_int, [C.POINTER(PlotsDesc), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p]),
     "prc_strack_workspace_bytes": (C.c_int, [C.POINTER(StrackDesc), C.c_int32, C.POINTER(C.c_size_t)]),
     "prc_strack_run": (C.c_int, [C.POINTER(StrackDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),

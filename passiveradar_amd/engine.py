@@ -446,6 +446,32 @@ def cfar_os_execute(desc, X, out, noise, nframes, workspace, stream=None):
     check(lib().prc_cfar_os(C.byref(desc), _ptr(X), _ptr(out), _ptr(noise), int(nframes), _ptr(workspace), stream))
 
 
+def plots_desc(H, W, thresh, frame_extent, connectivity=8, range_guard=8, doppler_guard=4, max_cells=None, capacity=512,
+               complex_weight=False):
+    """prc_plots_desc of include/prcore.h (max_cells None: PRC_PLOTS_LDS_CELLS, the most the LDS path holds)"""
+    d = _lib.PlotsDesc()
+    d.H, d.W, d.connectivity = int(H), int(W), int(connectivity)
+    d.range_guard, d.doppler_guard = int(range_guard), int(doppler_guard)
+    d.max_cells = _lib.PLOTS_LDS_CELLS if max_cells is None else int(max_cells)
+    d.capacity, d.weight_input, d.thresh = int(capacity), int(bool(complex_weight)), float(thresh)
+    d.doppler_extent, d.range_extent = float(frame_extent[0]), float(frame_extent[1])
+    return d
+
+
+def plots_workspace_bytes(desc, nframes):
+    """device bytes prc_plots needs in ``workspace`` (0 up to PRC_PLOTS_LDS_CELLS cells); validates the descriptor on the host"""
+    nb = C.c_size_t(0)
+    check(lib().prc_plots_workspace_bytes(C.byref(desc), int(nframes), C.byref(nb)))
+    return int(nb.value)
+
+
+def plots_execute(desc, stat, weight, nframes, counts, ncells, cands, info, workspace, stream=None):
+    """plot extraction of a stack (device buffers or torch tensors; ``weight``, ``info`` and, on the LDS path, ``workspace``
+    may be None)"""
+    check(lib().prc_plots(C.byref(desc), _ptr(stat), _ptr(weight), int(nframes), _ptr(counts), _ptr(ncells), _ptr(cands),
+                          _ptr(info), _ptr(workspace), stream))
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

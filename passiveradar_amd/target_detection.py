@@ -4,7 +4,8 @@ multitarget_kalman_tracker.py: ``get_measurements`` (:164-229) and ``multitarget
 ``track_maps``, that script's CFAR -> measure -> track chain (:44-63) in one device pass, and the single-target tracker
 of simple_kalman_tracker.py: ``simple_target_tracker`` (:626-681), plus ``simple_track_maps``, its CFAR -> track
 chain (:46-61).  Beyond the reference: ``CFAR_2D_OS``, the order-statistic CFAR on CFAR_2D's window (with
-``cfar_training_cells`` and ``os_cfar_threshold``), which the chains take with ``cfar="os"``, and ``refine_peaks``."""
+``cfar_training_cells`` and ``os_cfar_threshold``), which the chains take with ``cfar="os"``, ``refine_peaks``, and
+``extract_plots``, the plot extractor between a CFAR map and the tracker (``track_maps(..., measure="plots")``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,7 +18,7 @@ from ._lib import check, lib
 __all__ = ["CFAR_2D", "CFAR_2D_abs", "CFAR_2D_OS", "cfar_training_cells", "os_cfar_threshold", "get_measurements",
            "multitarget_tracker", "track_maps",
            "kalman_filter_dtype", "target_track_dtype", "simple_target_tracker", "simple_track_maps",
-           "target_track_dtype_simple", "refine_peaks"]
+           "target_track_dtype_simple", "refine_peaks", "extract_plots"]
 
 
 def CFAR_2D(X, fw, gw, thresh=None):
@@ -168,18 +169,19 @@ def CFAR_2D_OS(X, fw, gw, thresh=None, *, rank=None, scale="reference", return_n
     return (out, dz.download(x.shape, np.float32).astype(np.float64)) if return_noise else out
 
 
-def _chain_cfar(x, fw, gw, cfar, cfar_rank):
-    """the CFAR stage of the device chains on a torch stack: "mean" = CFAR_2D / CFAR_2D_abs, "os" = CFAR_2D_OS"""
+def _chain_cfar(x, fw, gw, cfar, cfar_rank, scale="reference"):
+    """the CFAR stage of the device chains on a torch stack: "mean" = CFAR_2D / CFAR_2D_abs, "os" = CFAR_2D_OS (``scale``
+    applies to it alone)"""
     if cfar == "os":
-        return CFAR_2D_OS(x, fw, gw, rank=cfar_rank)
+        return CFAR_2D_OS(x, fw, gw, rank=cfar_rank, scale=scale)
     if cfar != "mean":
         raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
     return CFAR_2D_abs(x, fw, gw) if x.is_complex() else CFAR_2D(x, fw, gw)
 
 
-def _chain_cfar_staged(x, fw, gw, cfar, cfar_rank):
+def _chain_cfar_staged(x, fw, gw, cfar, cfar_rank, scale="reference"):
     """the same stage for a host stack [nframes, H, W] on buffers the chain owns (null stream): returns
-    (maps buffer, nframes, H, W, what must stay alive)"""
+    (maps buffer, nframes, H, W, what must stay alive: the uploaded input first)"""
     if cfar not in ("mean", "os"):
         raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
     cplx = np.iscomplexobj(x)
@@ -190,7 +192,7 @@ def _chain_cfar_staged(x, fw, gw, cfar, cfar_rank):
     do = _lib.DeviceBuffer(nframes * H * W * 4)
     ws = None
     if cfar == "os":
-        desc = engine.cfar_os_desc(H, W, fw, gw, cfar_rank, "reference", cplx)
+        desc = engine.cfar_os_desc(H, W, fw, gw, cfar_rank, scale, cplx)
         ws = _lib.DeviceBuffer(engine.cfar_os_workspace_bytes(desc, nframes))
         engine.cfar_os_execute(desc, dx, do, None, nframes, ws)
     else:
@@ -398,11 +400,25 @@ def multitarget_tracker(data, frame_extent, N_TRACKS):
     return _records_to_history(m.run(), int(N_TRACKS))
 
 
-def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4, cfar="mean", cfar_rank=None):
+def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4, cfar="mean", cfar_rank=None, measure="percentile",
+               plot_thresh=None, plot_connectivity=8, plot_max_cells=None, plot_capacity=None):
     """multitarget_kalman_tracker.py:44-63 as one device chain on the caller's stream: CFAR_2D(|xambg|, fw, gw) per
     frame (CFAR_2D_abs; CFAR_2D for a real magnitude stack) -> get_measurements -> multitarget_tracker.  ``xambg`` is a
     torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it.  ``cfar="os"`` puts CFAR_2D_OS
-    (reference scale, rank ``cfar_rank``, default ceil(0.75 Nt)) in the cell average's place."""
+    (reference scale, rank ``cfar_rank``, default ceil(0.75 Nt)) in the cell average's place.
+    ``measure="plots"`` (beyond the reference) puts the plot extractor in get_measurements' place: the CFAR map is
+    thresholded at ``plot_thresh`` (required) and every connected cluster (``plot_connectivity``) is one measurement at its
+    centroid, weighted by |xambg| (extract_plots).  With ``cfar="os"`` the CFAR then runs on the ``plain`` scale, the one
+    os_cfar_threshold's multiplier applies to; with ``cfar="mean"`` on CFAR_2D's ratio.  ``plot_max_cells`` /
+    ``plot_capacity`` pin the extractor's bounds (default: sized from the counts); a frame over a pinned bound raises
+    PrcoreError, as the tracker's overflow does."""
+    if measure not in ("percentile", "plots"):
+        raise ValueError(f"measure is 'percentile' or 'plots', not {measure!r}")
+    if measure == "plots":
+        if plot_thresh is None:
+            raise ValueError("measure='plots' needs plot_thresh")
+        return _track_plots(xambg, frame_extent, int(N_TRACKS), fw, gw, cfar, cfar_rank, float(plot_thresh),
+                            plot_connectivity, plot_max_cells, plot_capacity)
     if _lib.is_device_tensor(xambg):
         cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
         if cf.dim() == 2:
@@ -413,6 +429,214 @@ def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4, cfar="mean", cfar_
     do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank)
     m = _Measured(do.ptr, nframes, H, W, frame_extent, int(N_TRACKS), lambda name, nb: _lib.DeviceBuffer(nb), None)
     return _records_to_history(m.run(), int(N_TRACKS))
+
+
+# ---- plot extraction (beyond the reference) -------------------------------------------------------
+PLOTS_DEFAULT_CAPACITY = 512
+
+
+class _Plots:
+    """counts + one prc_track_cand per plot of a stack of statistic frames on the device (prc_plots).  A bound left at
+    None is sized from what the call reports, as _Measured sizes its capacity: after a run ncells / counts are read, and if
+    a frame exceeded ``max_cells`` the stack is run again at the exact maximum (the workspace path if that is above
+    PRC_PLOTS_LDS_CELLS); if then, or at first, a frame has more plots than ``capacity``, once more at that exact maximum
+    (the plot count of a frame over max_cells is only known after the first re-run).  A pinned bound is never changed: the
+    caller sees the overflow in ncells / counts.  ``start_max_cells`` / ``start_capacity`` only replace the first guesses."""
+
+    def __init__(self, stat_ptr, weight_ptr, complex_weight, nframes, H, W, thresh, frame_extent, alloc, stream,
+                 connectivity=8, range_guard=8, doppler_guard=4, max_cells=None, capacity=None, want_info=False,
+                 start_max_cells=None, start_capacity=None):
+        self.alloc, self.stream, self.nframes = alloc, stream, nframes
+        mc = int(max_cells or start_max_cells or _lib.PLOTS_LDS_CELLS)
+        cap = int(capacity or start_capacity or PLOTS_DEFAULT_CAPACITY)
+        nf = max(nframes, 1)
+        self.counts_buf = alloc("plot_counts", 4 * nf)
+        self.ncells_buf = alloc("plot_ncells", 4 * nf)
+        self.runs = 0
+        while True:
+            desc = engine.plots_desc(H, W, thresh, frame_extent, connectivity, range_guard, doppler_guard, mc, cap,
+                                     complex_weight)
+            nws = engine.plots_workspace_bytes(desc, nframes)
+            self.cands_buf = alloc("plot_cands", 32 * nf * cap)
+            self.info_buf = alloc("plot_info", _lib.PLOT_INFO_DTYPE.itemsize * nf * cap) if want_info else None
+            ws = alloc("plot_ws", nws) if nws else None
+            check(lib().prc_memset(self.cands_buf.ptr, 0, 32 * nf * cap, stream))        # slots past a count read as zeros
+            if want_info:
+                check(lib().prc_memset(self.info_buf.ptr, 0, _lib.PLOT_INFO_DTYPE.itemsize * nf * cap, stream))
+            engine.plots_execute(desc, stat_ptr, weight_ptr, nframes, self.counts_buf.ptr, self.ncells_buf.ptr,
+                                 self.cands_buf.ptr, self.info_buf.ptr if want_info else None, ws.ptr if ws else None, stream)
+            self.runs += 1
+            self.counts = self.counts_buf.download(nframes, np.int32, stream=stream)
+            self.ncells = self.ncells_buf.download(nframes, np.int32, stream=stream)
+            need_mc = int(self.ncells.max()) if nframes else 0
+            need_cap = int(self.counts.max()) if nframes else 0
+            grow_mc = max_cells is None and need_mc > mc
+            grow_cap = capacity is None and need_cap > cap
+            if not (grow_mc or grow_cap) or self.runs == 3:
+                break
+            mc = need_mc if grow_mc else mc
+            cap = need_cap if grow_cap else cap
+        self.max_cells, self.capacity = mc, cap
+
+    def stored(self):
+        """plots written per frame"""
+        return np.minimum(self.counts, self.capacity)
+
+    def overflowed(self):
+        return bool((self.ncells > self.max_cells).any() or (self.counts > self.capacity).any())
+
+    def candidates(self):
+        raw = self.cands_buf.download(self.nframes * self.capacity, _lib.TRACK_CAND_DTYPE, stream=self.stream)
+        return raw.reshape(self.nframes, self.capacity)
+
+    def info(self):
+        raw = self.info_buf.download(self.nframes * self.capacity, _lib.PLOT_INFO_DTYPE, stream=self.stream)
+        return raw.reshape(self.nframes, self.capacity)
+
+
+def _plots_check_host(H, W, thresh, frame_extent, connectivity, range_guard, doppler_guard, max_cells, capacity, nframes):
+    """every argument check of prc_plots, on the host (ValueError), before a device is touched"""
+    for name, v in (("max_cells", max_cells), ("capacity", capacity)):
+        if v is not None and int(v) < 1:
+            raise ValueError(f"{name} = {v}, not >= 1")
+    desc = engine.plots_desc(H, W, thresh, frame_extent, connectivity, range_guard, doppler_guard, max_cells,
+                             PLOTS_DEFAULT_CAPACITY if capacity is None else capacity)
+    engine.plots_workspace_bytes(desc, nframes)
+
+
+def _device_plots(stat, thresh, frame_extent, weight, **kw):
+    """_Plots of a 2-D frame or [nframes, H, W] stack: numpy (staged, null stream) or a torch device tensor (its stream)"""
+    dev = _lib.is_device_tensor(stat)
+    if weight is not None and _lib.is_device_tensor(weight) != dev:
+        raise ValueError("stat and weight are both NumPy arrays or both device tensors")
+    if dev:
+        import torch
+        t = stat.to(torch.float32).contiguous()
+        w = None if weight is None else weight.to(torch.complex64 if weight.is_complex() else torch.float32).contiguous()
+        shape, wshape, cplx = tuple(t.shape), None if w is None else tuple(w.shape), w is not None and w.is_complex()
+    else:
+        t = np.ascontiguousarray(stat, dtype=np.float32)
+        w = None
+        if weight is not None:
+            w = np.asarray(weight)
+            w = np.ascontiguousarray(w, dtype=np.complex64 if np.iscomplexobj(w) else np.float32)
+        shape, wshape, cplx = t.shape, None if w is None else w.shape, w is not None and np.iscomplexobj(w)
+    if len(shape) not in (2, 3):
+        raise ValueError("extract_plots takes a frame [H, W] or a stack [nframes, H, W]")
+    if wshape is not None and wshape != shape:
+        raise ValueError(f"weight has shape {wshape}, stat {shape}")
+    nframes, H, W = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    _plots_check_host(H, W, thresh, frame_extent, kw.get("connectivity", 8), kw.get("range_guard", 8),
+                      kw.get("doppler_guard", 4), kw.get("max_cells"), kw.get("capacity"), nframes)
+    if dev:
+        stream = _lib.torch_stream_ptr(t.device)
+        with torch.cuda.device(t.device):
+            m = _Plots(t.data_ptr(), None if w is None else w.data_ptr(), cplx, nframes, H, W, thresh, frame_extent,
+                       lambda name, nb: _TorchBuf(nb, t.device), stream, **kw)
+        m.keep = (t, w)
+        return m
+    _lib.require_gpu()
+    dx = _lib.DeviceBuffer(t.nbytes)
+    dx.upload(t)
+    dw = None
+    if w is not None:
+        dw = _lib.DeviceBuffer(w.nbytes)
+        dw.upload(w)
+    m = _Plots(dx.ptr, None if dw is None else dw.ptr, cplx, nframes, H, W, thresh, frame_extent,
+               lambda name, nb: _lib.DeviceBuffer(nb), None, **kw)
+    m.keep = (dx, dw)
+    return m
+
+
+def extract_plots(stat, thresh, frame_extent, *, weight=None, connectivity=8, range_guard=8, doppler_guard=4,
+                  max_cells=None, capacity=None, return_info=False, start_max_cells=None, start_capacity=None):
+    """Plot extraction (prc_plots of include/prcore.h): the cells of a CFAR statistic with ``stat > thresh`` outside
+    get_measurements' excluded zones (``range_guard`` range columns at either end, ``doppler_guard`` Doppler columns either
+    side of zero; 0 switches a zone off), grouped into connected clusters (``connectivity`` 4 or 8), one measurement per
+    cluster: range and Doppler of the centroid weighted by ``weight`` (same shape; complex: its magnitude; default: stat
+    itself) and the cluster's largest stat as strength -- strongest first, ties as get_measurements breaks them.
+    A NumPy 2-D frame (H Doppler rows x W range columns) returns (3, M) float64 -- range, Doppler, strength --
+    get_measurements' shape.  A NumPy stack [N, H, W] or a torch device stack returns ``(counts, meas, index)`` as
+    get_measurements does for device stacks (int32 [N]; float64 [N, 3, capacity]; int64 [N, capacity]; entries past
+    counts[i] are zero), arrays for NumPy, tensors on the caller's device and torch's current stream for torch.
+    ``return_info=True`` appends the prc_plot_info records (a structured array of _lib.PLOT_INFO_DTYPE, [N, capacity] /
+    [M]; a uint8 tensor [N, capacity, 48] for torch) and ncells, the detecting cells per frame.
+    ``max_cells`` (detections held per frame, default PRC_PLOTS_LDS_CELLS) and ``capacity`` (plots stored per frame, default
+    512) left at None are sized from the counts: a frame over either makes the call run again at the exact maximum.  A
+    pinned bound is kept: counts[i] > capacity means only the first ``capacity`` plots were stored, ncells[i] > max_cells
+    that frame i was not extracted (counts[i] = 0).  ``start_max_cells`` / ``start_capacity`` replace the first guesses."""
+    thresh = float(thresh)
+    m = _device_plots(stat, thresh, frame_extent, weight, connectivity=connectivity, range_guard=range_guard,
+                      doppler_guard=doppler_guard, max_cells=max_cells, capacity=capacity, want_info=return_info,
+                      start_max_cells=start_max_cells, start_capacity=start_capacity)
+    N, cap = m.nframes, m.capacity
+    if _lib.is_device_tensor(stat):
+        import torch
+        raw = m.cands_buf.t[:32 * N * cap]
+        meas = raw.view(torch.float64).view(N, cap, 4)[:, :, [1, 2, 0]].permute(0, 2, 1).contiguous()
+        index = raw.view(torch.int64).view(N, cap, 4)[:, :, 3].contiguous()
+        counts = m.counts_buf.t[:4 * N].view(torch.int32).clone()
+        if not return_info:
+            return counts, meas, index
+        nb = _lib.PLOT_INFO_DTYPE.itemsize
+        return counts, meas, index, m.info_buf.t[:nb * N * cap].view(N, cap, nb).clone(), m.ncells_buf.t[:4 * N].view(torch.int32).clone()
+    c = m.candidates()
+    if len(np.shape(stat)) == 2:
+        k = int(m.stored()[0])
+        meas = _cands_to_meas(c[0], k)
+        return (meas, m.info()[0][:k], int(m.ncells[0])) if return_info else meas
+    meas = np.ascontiguousarray(np.stack((c["range"], c["doppler"], c["strength"]), axis=1))
+    out = (m.counts, meas, np.ascontiguousarray(c["index"]))
+    return out + (m.info(), m.ncells) if return_info else out
+
+
+def _track_plots(xambg, frame_extent, ntracks, fw, gw, cfar, cfar_rank, thresh, connectivity, max_cells, capacity):
+    """CFAR -> prc_plots -> prc_track_run on one stream; the maps themselves are the weights"""
+    if cfar not in ("mean", "os"):
+        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
+    dev = _lib.is_device_tensor(xambg)
+    if dev:
+        import torch
+        x = xambg.to(torch.complex64 if xambg.is_complex() else torch.float32).contiguous()
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        shape, cplx = tuple(x.shape), x.is_complex()
+    else:
+        x = np.asarray(xambg)
+        if x.ndim != 3:
+            raise ValueError("track_maps takes (H, W, Nframes) frames")
+        x = np.moveaxis(x, 2, 0)
+        shape, cplx = x.shape, np.iscomplexobj(x)
+    if len(shape) != 3:
+        raise ValueError("track_maps takes a device stack [N, H, W]")
+    nframes, H, W = (int(v) for v in shape)
+    _plots_check_host(H, W, thresh, frame_extent, connectivity, 8, 4, max_cells, capacity, nframes)
+    kw = dict(connectivity=connectivity, max_cells=max_cells, capacity=capacity)
+    if dev:
+        cf = _chain_cfar(x, fw, gw, cfar, cfar_rank, "plain")
+        stream = _lib.torch_stream_ptr(x.device)
+        alloc = lambda name, nb: _TorchBuf(nb, x.device)      # noqa: E731
+        with torch.cuda.device(x.device):
+            m = _Plots(cf.data_ptr(), x.data_ptr(), cplx, nframes, H, W, thresh, frame_extent, alloc, stream, **kw)
+            rec = _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, stream)
+    else:
+        _lib.require_gpu()
+        do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank, "plain")
+        alloc = lambda name, nb: _lib.DeviceBuffer(nb)        # noqa: E731
+        m = _Plots(do.ptr, keep[0].ptr, cplx, nframes, H, W, thresh, frame_extent, alloc, None, **kw)
+        rec = _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, None)
+    return _records_to_history(rec, ntracks)
+
+
+def _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, stream):
+    if (m.ncells > m.max_cells).any():
+        raise _lib.PrcoreError(_lib.PRC_EINVAL, "track_maps: a frame's detections exceeded plot_max_cells")
+    plan = TrackPlan(H, W, ntracks, m.capacity, frame_extent)
+    rec = alloc("records", 256 * max(m.nframes, 1) * ntracks)
+    plan.run(m.counts_buf.ptr, m.cands_buf.ptr, m.nframes, rec.ptr, stream)
+    out = rec.download(m.nframes * ntracks, _lib.TRACK_RECORD_DTYPE, stream=stream)
+    plan.close()
+    return out.reshape(m.nframes, ntracks)
 
 
 # ---- single-target tracker (target_detection.py:530-681) ---------------------------------------------------------------
