@@ -35,7 +35,8 @@
  *     (tests/test_gpu_bounds.py holds every single-rank device entry point to this; tests/test_gpu_display.py the
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
- *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots).
+ *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots, tests/test_gpu_tbd_bounds.py prc_tbd and
+ *     prc_tbd_trace).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -52,7 +53,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, fourth edition (additions only, the number stays as for the editions below): prc_plots_desc, prc_plot_info,
+#define PRC_VERSION 680   /* 680, fifth edition (additions only, the number stays as for the editions below): prc_tbd_desc, prc_tbd, prc_tbd_trace,
+                             PRC_OPT_TBD_FRAMES, PRC_OPT_TBD_ROWS (track-before-detect: Viterbi integration of a stack of CFAR maps, on device);
+                             680, fourth edition (additions only, the number stays as for the editions below): prc_plots_desc, prc_plot_info,
                              prc_plots_workspace_bytes, prc_plots (plot extraction: CFAR detections clustered into plots, on device);
                              680, third edition (additions only, no layout of 680 changed, so the number stays: a host checks for the new
                              entry points by symbol): prc_eca_workspace_bytes, prc_eca_execute, prc_eca_set_profiling, prc_eca_get_profile
@@ -146,7 +149,13 @@ typedef enum prc_option {
     PRC_OPT_FE_FOLD = 14,         /* front-end group kernel, read per launch: 1 (default) = FOLDED tap rows where they apply (odd decimation:
                                      rows rho and rho + M of the banded tap table never meet the same output, so they share one row of
                                      full width: 184 rows instead of 294 at 13:119, no multiply-adds on zero taps); 0 = the unfolded rows  */
-    PRC_OPT_COUNT_ = 15
+    PRC_OPT_TBD_FRAMES = 15,      /* prc_tbd, read per call: frames one launch advances.  0 (default) = the shipped choice (PRC_TBD_FRAMES
+                                     in the time-blocked form where a frame is narrow enough for it, see prc_tbd); 1 = one frame per
+                                     launch; 2 .. PRC_TBD_FRAMES_MAX = the time-blocked form with that many frames (fewer, down to 2,
+                                     where LDS does not hold them; one frame per launch where it holds none).  Same bytes out at every value */
+    PRC_OPT_TBD_ROWS = 16,        /* prc_tbd, read per call: rows of the band a workgroup of the time-blocked form owns.  0 (default) =
+                                     from the shape (see prc_tbd); 1 .. 4096 = forced (lowered to what LDS holds).  Same bytes out       */
+    PRC_OPT_COUNT_ = 17
 } prc_option;
 int prc_set_option(int32_t option, int64_t value);     /* PRC_EINVAL for an unknown option or a value out of range */
 int prc_get_option(int32_t option, int64_t* value);
@@ -663,6 +672,64 @@ int prc_plots_workspace_bytes(const prc_plots_desc* desc, int32_t nframes, size_
 int prc_plots(const prc_plots_desc* desc, const float* stat, const void* weight /* or NULL */, int32_t nframes,
               int32_t* counts, int32_t* ncells_out, prc_track_cand* cands /* [nframes][capacity] */,
               prc_plot_info* info /* or NULL, [nframes][capacity] */, void* workspace, void* stream);
+
+/* ---- track-before-detect: Viterbi (dynamic-programming) integration of a stack of statistic frames: DESIGN.md section 21 ---- */
+/* Beyond the reference (which decides every detection in one frame): a per-cell statistic is integrated along every admissible
+ * path through the frame stack; per cell and frame the best accumulated score and a back pointer are kept (Barniv 1985;
+ * Tonissen & Evans 1996).  tests/tbd_oracle.py is this definition in NumPy; the device result equals it bit for bit (the
+ * sign and payload of a NaN excepted, which IEEE 754 leaves open).
+ * Layout: stat, score: DEVICE float32 [nframes][H][W] (h = Doppler row, w = range column, as prc_cfar2d / prc_cfar_os / prc_plots);
+ *   back: DEVICE uint8 [nframes][H][W] or NULL; row_shift: DEVICE int32 [H] or NULL (= all zero), any values; prev: DEVICE
+ *   float32 [H][W] or NULL, the score of the frame before the call.
+ * Input cell z'_k[h, w]: 0.0f inside an excluded zone (prc_plots' two masks with prc_plots' meaning of range_guard and
+ *   doppler_guard: w < range_guard or w >= W - range_guard; Doppler column c = H-1-h inside [H/2 - doppler_guard,
+ *   H/2 + doppler_guard)); otherwise z if not (z > clip), else clip (a NaN stays a NaN; clip = +Inf switches clipping off).
+ * Predecessors of (h, w): for dh in [-qd, qd] (outer loop), dw in [-qr, qr] (inner loop), qd = doppler_reach, qr = range_reach,
+ *   code = (dh + qd)(2 qr + 1) + (dw + qr): the cell h' = h + dh, w' = w - row_shift[h'] + dw (the shift of the PREDECESSOR's
+ *   row: a row's shift is the number of range columns an echo at that row's Doppler advances per frame), evaluated without
+ *   overflow for any int32 shift; it counts only if 0 <= h' < H and 0 <= w' < W.
+ * Choice: best = -Inf, none chosen; over ascending codes an in-bounds predecessor with v = I_{k-1}[h', w'] is chosen iff
+ *   v > best (float32 compare): a NaN or -Inf is never chosen, ties go to the smallest code.  back_k[h, w] = the chosen code,
+ *   255 if none; m = the chosen v, 0.0f if none.
+ * Recursion: I_k = z'_k + alpha m, the product and the sum each rounded to float32 on its own (no fused multiply-add).  Frame 0
+ *   takes `prev` as I_{-1} when it is given; without it I_0 = z'_0 and back_0 = 255.  score[k] = I_k.  To continue a stream, pass
+ *   the last score frame of one call as `prev` of the next: the result is that of one call over both stacks.
+ * prc_tbd_trace: for end e = (frame f, storage cell c = h W + w) of ends [nends][2], paths[e][0] = c; for j >= 1 the code is
+ *   back[f-j+1][paths[e][j-1]]: on 255, on a code >= ncodes, when f - j < 0 or when the predecessor formula leaves the frame (a
+ *   `back` array that prc_tbd did not write), this entry and all later ones are -1; otherwise paths[e][j] = the predecessor cell
+ *   (it lies in frame f - j).  An end whose frame is outside [0, nframes) or whose cell is outside [0, H W) gives a row of -1.
+ *   Nothing outside back [nframes][H][W], row_shift [H], ends and paths [nends][depth] is touched.
+ * Kernels.  The recursion is sequential in k and parallel in the cells.  Time-blocked form: a workgroup owns a band of B rows
+ *   at full width, keeps two score buffers of B + 2 K qd rows of W + 2 qr floats in LDS (every row staged with its shift applied
+ *   and -Inf where no predecessor exists) and advances K frames per launch, recomputing a halo of K qd rows on either side:
+ *   ceil(nframes / K) launches.  It runs where 2 frames fit: 8 (W + 2 qr)(1 + 4 qd) <= PRC_TBD_LDS_BYTES, i.e. W <= 3991 at reach
+ *   (1, 1); K = PRC_TBD_FRAMES (PRC_OPT_TBD_FRAMES overrides), lowered while B >= 1 does not fit; B = ceil(H / 256), one
+ *   workgroup per compute unit (PRC_OPT_TBD_ROWS overrides), lowered to what LDS holds.  Wider frames run one frame per
+ *   launch from global memory (the same device code for z', the choice and the sum).  Both forms, every K and every B write the
+ *   same bytes.  Frames are ordered by launches on `stream` alone: no workgroup waits for another.
+ * Neither call allocates, frees, copies or synchronises; both can be captured.  No atomics: the bytes out are a pure function
+ * of the arguments.  Element alignment suffices.  score must not overlap stat or prev.
+ * PRC_ESHAPE: H or W < 1, H W > 2^31 - 1.  PRC_EINVAL: a bad descriptor header, a negative reach or guard, more than 255 codes,
+ * alpha not in (0, 1], a NaN clip, depth < 1, nframes or nends < 0, a null stat / score (prc_tbd, nframes > 0) or back / ends /
+ * paths (prc_tbd_trace, nends > 0).  Every check is host arithmetic and needs no device; nframes == 0 and nends == 0 are no-ops. */
+#define PRC_TBD_FRAMES 8            /* K of the shipped time-blocked form (DESIGN.md section 21 has the measurements) */
+#define PRC_TBD_FRAMES_MAX 32
+#define PRC_TBD_LDS_BYTES 159744    /* 156 KiB of the 160 KiB a CDNA4 workgroup can address */
+typedef struct prc_tbd_desc {
+    uint32_t struct_size;  /* sizeof(prc_tbd_desc) as the host compiled it (see Conventions)                   */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                                    */
+    int32_t H, W;          /* Doppler rows, range columns of a frame (>= 1 each)                                */
+    int32_t doppler_reach, range_reach;   /* qd, qr >= 0, (2 qd + 1)(2 qr + 1) <= 255                           */
+    int32_t range_guard, doppler_guard;   /* >= 0, as prc_plots_desc                                            */
+    float alpha;           /* forgetting factor in (0, 1]                                                       */
+    float clip;            /* largest z' (+Inf: off; NaN: PRC_EINVAL)                                           */
+} prc_tbd_desc;
+#define PRC_TBD_DESC_SIZE_MIN 40u
+int prc_tbd(const prc_tbd_desc* desc, const float* stat, const int32_t* row_shift /* or NULL */, const float* prev /* or NULL */,
+            int32_t nframes, float* score /* [nframes][H][W] */, uint8_t* back /* or NULL */, void* stream);
+int prc_tbd_trace(const prc_tbd_desc* desc, const uint8_t* back, const int32_t* row_shift /* or NULL */, int32_t nframes,
+                  const int32_t* ends /* [nends][2]: frame, cell */, int32_t nends, int32_t depth, int32_t* paths /* [nends][depth] */,
+                  void* stream);
 
 /* ---- single-target tracker: target_detection.py:530-681 (simple_target_tracker) ------------------------------------ */
 /* Frames are [nframes][H][W] (H Doppler rows, W range columns), float32 (the CFAR output) or float64.  The result is the

@@ -23,7 +23,7 @@ CAF_MULTI_MODES = {"auto": CAF_MULTI_AUTO, "turns": CAF_MULTI_TURNS, "shared": C
 # prc_option
 (OPT_CAF_MULTI_MODE, OPT_CAF_GROUP_MB, OPT_LS_TEAM_PIECES, OPT_LS_TEAM_ALIGN, OPT_NLMS_WAVES, OPT_LS_CACHE_LIMIT_MB,
  OPT_NLMS_WG_WAVES, OPT_CAF_XCD_CONTIG, OPT_CAF_PAIR_FRAMES, OPT_FE_METHOD,
- OPT_CFAR_METHOD, OPT_MARKERS, OPT_FE_BALANCE, OPT_CAF_TEAM8, OPT_FE_FOLD) = range(15)
+ OPT_CFAR_METHOD, OPT_MARKERS, OPT_FE_BALANCE, OPT_CAF_TEAM8, OPT_FE_FOLD, OPT_TBD_FRAMES, OPT_TBD_ROWS) = range(17)
 CAF_MAX_REFS = 8
 COMM_ID_BYTES = 128
 
@@ -169,6 +169,17 @@ PLOT_INFO_DTYPE = np.dtype([("mass", "<f8"), ("hbar", "<f8"), ("wbar", "<f8"), (
                             ("w0", "<i4"), ("w1", "<i4"), ("peak", "<i4")])
 PLOTS_LDS_CELLS = 4096       # PRC_PLOTS_LDS_CELLS: detections per frame prc_plots holds in LDS (above: the caller's workspace)
 
+
+class TbdDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("H", C.c_int32), ("W", C.c_int32), ("doppler_reach", C.c_int32), ("range_reach", C.c_int32),
+                ("range_guard", C.c_int32), ("doppler_guard", C.c_int32), ("alpha", C.c_float), ("clip", C.c_float)]
+
+
+TBD_FRAMES, TBD_FRAMES_MAX = 8, 32      # PRC_TBD_FRAMES, PRC_TBD_FRAMES_MAX: frames per launch of prc_tbd's time-blocked form
+TBD_LDS_BYTES = 159744                  # PRC_TBD_LDS_BYTES
+TBD_NONE = 255                          # the back pointer of a cell without a predecessor
+
 FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
 
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
@@ -273,6 +284,9 @@ _SIGNATURES = {
     "prc_plots_workspace_bytes": (C.c_int, [C.POINTER(PlotsDesc), C.c_int32, C.POINTER(C.c_size_t)]),
     "prc_plots": (C.c_int, [C.POINTER(PlotsDesc), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p]),
+    "prc_tbd": (C.c_int, [C.POINTER(TbdDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "prc_tbd_trace": (C.c_int, [C.POINTER(TbdDesc), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                C.c_void_p]),
     "prc_strack_workspace_bytes": (C.c_int, [C.POINTER(StrackDesc), C.c_int32, C.POINTER(C.c_size_t)]),
     "prc_strack_run": (C.c_int, [C.POINTER(StrackDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),

@@ -472,6 +472,37 @@ def plots_execute(desc, stat, weight, nframes, counts, ncells, cands, info, work
                           _ptr(info), _ptr(workspace), stream))
 
 
+def tbd_desc(H, W, alpha=0.9, doppler_reach=1, range_reach=1, clip=None, range_guard=8, doppler_guard=4):
+    """prc_tbd_desc of include/prcore.h (clip None: +Inf, no clipping)"""
+    d = _lib.TbdDesc()
+    d.H, d.W, d.doppler_reach, d.range_reach = int(H), int(W), int(doppler_reach), int(range_reach)
+    d.range_guard, d.doppler_guard = int(range_guard), int(doppler_guard)
+    d.alpha, d.clip = float(alpha), float("inf") if clip is None else float(clip)
+    return d
+
+
+def tbd_execute(desc, stat, row_shift, prev, nframes, score, back, stream=None, frames_per_launch=None, band_rows=None):
+    """track-before-detect scores (and back pointers) of a stack (device buffers or torch tensors; ``row_shift``, ``prev`` and
+    ``back`` may be None).  ``frames_per_launch`` / ``band_rows`` (tests and tools only) set PRC_OPT_TBD_FRAMES /
+    PRC_OPT_TBD_ROWS for this call: 1 = one frame per launch, 2 .. 32 = the time-blocked form; the bytes out do not change."""
+    old = []
+    try:
+        for opt, v in ((_lib.OPT_TBD_FRAMES, frames_per_launch), (_lib.OPT_TBD_ROWS, band_rows)):
+            if v is not None:
+                old.append((opt, _lib.set_option(opt, v)))
+        check(lib().prc_tbd(C.byref(desc), _ptr(stat), _ptr(row_shift), _ptr(prev), int(nframes), _ptr(score), _ptr(back), stream))
+    finally:
+        for opt, v in old:
+            _lib.set_option(opt, v)
+
+
+def tbd_trace(desc, back, row_shift, nframes, ends, nends, depth, paths, stream=None):
+    """paths [nends][depth] of storage cells read back through ``back`` from ``ends`` [nends][2] = (frame, cell); -1 from
+    where a path stops"""
+    check(lib().prc_tbd_trace(C.byref(desc), _ptr(back), _ptr(row_shift), int(nframes), _ptr(ends), int(nends), int(depth),
+                              _ptr(paths), stream))
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

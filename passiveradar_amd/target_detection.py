@@ -5,7 +5,9 @@ multitarget_kalman_tracker.py: ``get_measurements`` (:164-229) and ``multitarget
 of simple_kalman_tracker.py: ``simple_target_tracker`` (:626-681), plus ``simple_track_maps``, its CFAR -> track
 chain (:46-61).  Beyond the reference: ``CFAR_2D_OS``, the order-statistic CFAR on CFAR_2D's window (with
 ``cfar_training_cells`` and ``os_cfar_threshold``), which the chains take with ``cfar="os"``, ``refine_peaks``, and
-``extract_plots``, the plot extractor between a CFAR map and the tracker (``track_maps(..., measure="plots")``)."""
+``extract_plots``, the plot extractor between a CFAR map and the tracker (``track_maps(..., measure="plots")``), and
+track-before-detect: ``track_before_detect`` (the Viterbi integration of a stack of CFAR maps along the paths the Doppler
+rows allow, ``tbd_row_shifts``), ``tbd_paths`` and the chain ``tbd_maps``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +20,8 @@ from ._lib import check, lib
 __all__ = ["CFAR_2D", "CFAR_2D_abs", "CFAR_2D_OS", "cfar_training_cells", "os_cfar_threshold", "get_measurements",
            "multitarget_tracker", "track_maps",
            "kalman_filter_dtype", "target_track_dtype", "simple_target_tracker", "simple_track_maps",
-           "target_track_dtype_simple", "refine_peaks", "extract_plots"]
+           "target_track_dtype_simple", "refine_peaks", "extract_plots", "tbd_row_shifts", "track_before_detect", "tbd_paths",
+           "tbd_maps"]
 
 
 def CFAR_2D(X, fw, gw, thresh=None):
@@ -637,6 +640,209 @@ def _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, stream):
     out = rec.download(m.nframes * ntracks, _lib.TRACK_RECORD_DTYPE, stream=stream)
     plan.close()
     return out.reshape(m.nframes, ntracks)
+
+
+# ---- track-before-detect (beyond the reference) ---------------------------------------------------
+def tbd_row_shifts(H, W, frame_extent, frame_interval, wavelength):
+    """Range columns an echo in Doppler row h advances per frame, int32 [H], for prc_tbd's ``row_shift``.  Bistatic Doppler
+    is bistatic range rate, f = -(1/lambda) dR/dt, so on the axes of get_measurements / prc_plots (Doppler of row h:
+    f_h = D - h 2D/(H-1) Hz, evaluated as (H-1-2h) D/(H-1) so that s[h] = -s[H-1-h] holds exactly; range of column w:
+    R - w R/(W-1) km; [D, R] = frame_extent) s[h] = rint(lambda f_h dt (W-1) / (1000 R)) in float64, ``frame_interval`` dt in
+    seconds, ``wavelength`` in metres.  Positive Doppler is closing: the range falls and w rises."""
+    H, W = int(H), int(W)
+    D, R = float(frame_extent[0]), float(frame_extent[1])
+    dt, lam = float(frame_interval), float(wavelength)
+    if H < 2 or W < 2:
+        raise ValueError(f"H = {H}, W = {W}: the axes need at least two rows and two columns")
+    if not (np.isfinite(D) and np.isfinite(R) and R != 0.0 and np.isfinite(dt) and np.isfinite(lam)):
+        raise ValueError("frame_extent, frame_interval and wavelength must be finite, the range extent not zero")
+    f = (H - 1 - 2 * np.arange(H, dtype=np.float64)) * D / (H - 1)
+    s = np.rint(lam * f * dt * (W - 1) / (1000.0 * R))
+    if np.abs(s).max() > 2**31 - 1:
+        raise ValueError("a row shift does not fit int32")
+    return s.astype(np.int32)
+
+
+def _tbd_shifts_host(row_shifts, H):
+    """int32 [H] on the host from whatever the caller passed (None stays None)"""
+    if row_shifts is None:
+        return None
+    s = np.asarray(row_shifts.cpu() if hasattr(row_shifts, "cpu") else row_shifts)
+    if s.shape != (H,) or s.dtype.kind not in "iu":
+        raise ValueError(f"row_shifts must be {H} integers, one per Doppler row")
+    if s.size and (s.min() < -2**31 or s.max() > 2**31 - 1):
+        raise ValueError("a row shift does not fit int32")
+    return np.ascontiguousarray(s, dtype=np.int32)
+
+
+def _tbd_check_host(desc):
+    """every argument check of prc_tbd, on the host (ValueError), before a device is touched"""
+    check(lib().prc_tbd(C.byref(desc), None, None, None, 0, None, None, None))
+
+
+def track_before_detect(stat, frame_extent=None, *, alpha=0.9, doppler_reach=1, range_reach=1, row_shifts=None, clip=None,
+                        range_guard=8, doppler_guard=4, prev=None, return_back=True):
+    """Track-before-detect (prc_tbd of include/prcore.h): the Viterbi integration of a stack of statistic frames.  Per cell
+    and frame, score = z' + alpha max(score of the previous frame over the admissible predecessors): the cells within
+    (``doppler_reach``, ``range_reach``) of the cell moved back by its row's entry of ``row_shifts`` (int32 [H], range columns
+    per frame: tbd_row_shifts; None = no motion); z' is the statistic, 0 inside extract_plots' excluded zones
+    (``range_guard``, ``doppler_guard``) and at most ``clip``.  ``back`` holds the chosen predecessor's code per cell (255: none):
+    tbd_paths reads tracks back through it.  ``prev`` [H, W] is the score of the frame before the stack: passing a call's last
+    score frame to the next call continues the stream exactly.  ``frame_extent`` is not needed (the shifts carry the geometry)
+    and accepted only so that the call reads like extract_plots'.
+    ``stat`` is a frame [H, W] or a stack [N, H, W] (H Doppler rows, W range columns), NumPy or a torch device tensor;
+    returns ``(score, back)`` of stat's shape, float32 and uint8 (back None with ``return_back=False``): arrays for NumPy,
+    tensors on the caller's device and torch's current stream for torch."""
+    dev = _lib.is_device_tensor(stat)
+    if dev:
+        import torch
+        t = stat.to(torch.float32).contiguous()
+        shape = tuple(t.shape)
+    else:
+        t = np.ascontiguousarray(stat, dtype=np.float32)
+        shape = t.shape
+    if len(shape) not in (2, 3):
+        raise ValueError("track_before_detect takes a frame [H, W] or a stack [nframes, H, W]")
+    nframes, H, W = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    desc = engine.tbd_desc(H, W, alpha, doppler_reach, range_reach, clip, range_guard, doppler_guard)
+    _tbd_check_host(desc)
+    s = _tbd_shifts_host(row_shifts, H)
+    if prev is not None and tuple(prev.shape) != (H, W):
+        raise ValueError(f"prev has shape {tuple(prev.shape)}, a frame {(H, W)}")
+    if dev:
+        if prev is not None and not _lib.is_device_tensor(prev):
+            raise ValueError("stat and prev are both NumPy arrays or both device tensors")
+        ds = None if s is None else torch.from_numpy(s).to(t.device)
+        dp = None if prev is None else prev.to(torch.float32).contiguous()
+        score = torch.empty_like(t)
+        back = torch.empty(shape, dtype=torch.uint8, device=t.device) if return_back else None
+        if nframes:
+            with torch.cuda.device(t.device):
+                engine.tbd_execute(desc, t, ds, dp, nframes, score, back, _lib.torch_stream_ptr(t.device))
+        return score, back
+    _lib.require_gpu()
+    n = nframes * H * W
+    if n == 0:
+        return np.zeros(shape, np.float32), (np.zeros(shape, np.uint8) if return_back else None)
+    dx, dscore = _lib.DeviceBuffer(4 * n), _lib.DeviceBuffer(4 * n)
+    dx.upload(t)
+    dback = _lib.DeviceBuffer(n) if return_back else None
+    ds = dp = None
+    if s is not None:
+        ds = _lib.DeviceBuffer(4 * H)
+        ds.upload(s)
+    if prev is not None:
+        dp = _lib.DeviceBuffer(4 * H * W)
+        dp.upload(np.ascontiguousarray(prev, dtype=np.float32))
+    engine.tbd_execute(desc, dx, ds, dp, nframes, dscore, dback)
+    return dscore.download(shape, np.float32), (dback.download(shape, np.uint8) if return_back else None)
+
+
+def tbd_paths(back, ends, depth, row_shifts=None, *, doppler_reach=1, range_reach=1):
+    """Read tracks back through track_before_detect's ``back`` [N, H, W] (prc_tbd_trace): ``ends`` [nends, 2] = (frame,
+    storage cell h W + w); returns int32 [nends, depth]: column 0 the end's own cell, column j the cell in frame - j, -1 from
+    where the path stops (no predecessor was chosen, the stack begins) and in the whole row of an end outside the stack.
+    ``row_shifts`` and the reaches are those of the track_before_detect call.  NumPy in, NumPy out; torch device tensors in,
+    a tensor on the same device and torch's current stream out."""
+    dev = _lib.is_device_tensor(back)
+    if len(back.shape) != 3:
+        raise ValueError("back is a stack [nframes, H, W]")
+    nframes, H, W = (int(v) for v in back.shape)
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError(f"depth = {depth}, not >= 1")
+    desc = engine.tbd_desc(H, W, 1.0, doppler_reach, range_reach)
+    _tbd_check_host(desc)
+    s = _tbd_shifts_host(row_shifts, H)
+    if dev:
+        import torch
+        b = back.to(torch.uint8).contiguous()
+        e = torch.as_tensor(ends, device=b.device).to(torch.int32).contiguous()
+        if e.dim() != 2 or e.shape[1] != 2:
+            raise ValueError("ends is [nends, 2]: frame, cell")
+        paths = torch.empty((e.shape[0], depth), dtype=torch.int32, device=b.device)
+        ds = None if s is None else torch.from_numpy(s).to(b.device)
+        if e.shape[0]:
+            with torch.cuda.device(b.device):
+                engine.tbd_trace(desc, b, ds, nframes, e, e.shape[0], depth, paths, _lib.torch_stream_ptr(b.device))
+        return paths
+    b = np.ascontiguousarray(back, dtype=np.uint8)
+    e = np.ascontiguousarray(ends, dtype=np.int32)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError("ends is [nends, 2]: frame, cell")
+    if e.shape[0] == 0:
+        return np.zeros((0, depth), np.int32)
+    _lib.require_gpu()
+    db, de, dpaths = _lib.DeviceBuffer(b.nbytes), _lib.DeviceBuffer(e.nbytes), _lib.DeviceBuffer(4 * e.shape[0] * depth)
+    db.upload(b)
+    de.upload(e)
+    ds = None
+    if s is not None:
+        ds = _lib.DeviceBuffer(4 * H)
+        ds.upload(s)
+    engine.tbd_trace(desc, db, ds, nframes, de, e.shape[0], depth, dpaths)
+    return dpaths.download((e.shape[0], depth), np.int32)
+
+
+def tbd_maps(xambg, frame_extent, frame_interval, wavelength, *, thresh, depth=16, fw=18, gw=4, cfar="os", cfar_rank=None,
+             plot_connectivity=8, **tbd_kw):
+    """CFAR -> track_before_detect -> extract_plots on the integrated score -> tbd_paths, stage after stage on the device:
+    the multi-frame counterpart of ``track_maps(measure="plots")``'s first two stages.  ``xambg`` is a torch device tensor
+    [N, H, W] or NumPy (H, W, Nframes) as track_maps takes it.  The CFAR is CFAR_2D_OS on the ``plain`` scale (``cfar="os"``)
+    or CFAR_2D / CFAR_2D_abs (``"mean"``); the row shifts are tbd_row_shifts(H, W, frame_extent, frame_interval, wavelength)
+    unless ``row_shifts`` is given; ``tbd_kw`` are track_before_detect's keywords.  The score stack is thresholded at
+    ``thresh`` (calibrate it on noise: the integrated score has no closed-form threshold here) and clustered with the score
+    as weight and the same guards; every plot's peak cell is the end of one path of ``depth`` cells.
+    Returns ``(counts, meas, index, paths)``: the first three as extract_plots returns them for a stack, ``paths`` int32
+    [N, capacity, depth] (tbd_paths' rows; -1 in the slots past counts[i])."""
+    if cfar not in ("mean", "os"):
+        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
+    dev = _lib.is_device_tensor(xambg)
+    if dev:
+        import torch
+        x = xambg if xambg.dim() == 3 else xambg.unsqueeze(0)
+        x = x.to(torch.complex64 if x.is_complex() else torch.float32).contiguous()
+    else:
+        x = np.asarray(xambg)
+        if x.ndim != 3:
+            raise ValueError("tbd_maps takes (H, W, Nframes) frames")
+        x = np.moveaxis(x, 2, 0)
+    if len(x.shape) != 3:
+        raise ValueError("tbd_maps takes a device stack [N, H, W]")
+    N, H, W = (int(v) for v in x.shape)
+    kw = dict(tbd_kw)
+    bad = set(kw) - {"alpha", "doppler_reach", "range_reach", "row_shifts", "clip", "range_guard", "doppler_guard", "prev"}
+    if bad:
+        raise TypeError(f"tbd_maps: unexpected keyword(s) {sorted(bad)}")
+    if kw.get("row_shifts") is None:
+        kw["row_shifts"] = tbd_row_shifts(H, W, frame_extent, frame_interval, wavelength)
+    guards = dict(range_guard=kw.get("range_guard", 8), doppler_guard=kw.get("doppler_guard", 4))
+    _tbd_check_host(engine.tbd_desc(H, W, kw.get("alpha", 0.9), kw.get("doppler_reach", 1), kw.get("range_reach", 1),
+                                    kw.get("clip"), **guards))
+    _plots_check_host(H, W, float(thresh), frame_extent, plot_connectivity, guards["range_guard"], guards["doppler_guard"],
+                      None, None, N)
+    if cfar == "os":
+        cf = CFAR_2D_OS(x, fw, gw, rank=cfar_rank, scale="plain")
+    elif dev:
+        cf = _chain_cfar(x, fw, gw, cfar, cfar_rank)
+    else:
+        cf = CFAR_2D_abs(x, fw, gw) if np.iscomplexobj(x) else CFAR_2D(x, fw, gw)
+    score, back = track_before_detect(cf, frame_extent, **kw)
+    counts, meas, index, info, _ = extract_plots(score, thresh, frame_extent, connectivity=plot_connectivity, return_info=True,
+                                                 **guards)
+    cap = int(index.shape[1])
+    if dev:
+        peak = info[:, :, 44:48].contiguous().view(torch.int32).view(N, cap)          # prc_plot_info.peak
+        valid = torch.arange(cap, device=x.device)[None, :] < counts[:, None]
+        frame = torch.arange(N, device=x.device, dtype=torch.int32)[:, None].expand(N, cap)
+        ends = torch.stack((torch.where(valid, frame, -1), torch.where(valid, peak, -1)), dim=2).to(torch.int32)
+    else:
+        valid = np.arange(cap)[None, :] < counts[:, None]
+        frame = np.broadcast_to(np.arange(N, dtype=np.int32)[:, None], (N, cap))
+        ends = np.stack((np.where(valid, frame, -1), np.where(valid, info["peak"], -1)), axis=2).astype(np.int32)
+    paths = tbd_paths(back, ends.reshape(N * cap, 2), depth, kw["row_shifts"], doppler_reach=kw.get("doppler_reach", 1),
+                      range_reach=kw.get("range_reach", 1))
+    return counts, meas, index, paths.reshape(N, cap, int(depth))
 
 
 # ---- single-target tracker (target_detection.py:530-681) ---------------------------------------------------------------
