@@ -20,20 +20,13 @@
 // The loop is exact for every finite input and bounded for any bit pattern: NaNs are just keys.
 #include "common.h"
 #include "cfar_mean.h"
+#include "order_select.h"
 
 #define CO_TX 64          // outputs per workgroup: 16 rows x 64 columns, 256 threads x 4 adjacent columns
 #define CO_TY 16
 #define CO_R 4
 #define CO_INTERP_STEPS 12                    // steps whose pivot is interpolated from the two counts; then midpoints
 #define CO_MAX_STEPS (CO_INTERP_STEPS + 33)   // a midpoint step halves the interval's width: 32 of them reach lo == hm from any start
-
-__device__ __forceinline__ uint32_t co_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float co_unkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 __host__ __device__ inline int co_pitch(int fw) { return (CO_TX + fw - 1 + (CO_R - 1) + 3) & ~3; }
 
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(256) void cfar_os_kernel(const TIn* __restrict__ X,
             int jj = (j0 + c - (fw - 1) + tx) % W;
             if (jj < 0) jj += W;
             for (int s_ = tx; s_ < tw; s_ += 64) {
-                const uint32_t k = co_key(cfar_mag(x[(int64_t)ii * W + jj]));
+                const uint32_t k = prc_okey_raw(cfar_mag(x[(int64_t)ii * W + jj]));
                 tile[r * pitch + s_] = k;
                 kmin = min(kmin, k), kmax = max(kmax, k);
                 jj += sstep;
@@ -191,8 +184,8 @@ __global__ __launch_bounds__(256) void cfar_os_kernel(const TIn* __restrict__ X,
     for (int o = 0; o < CO_R; ++o) {
         if (jq + o >= W) break;
         const uint32_t ans = flip[o] ? hm[o] - m[o] : lo[o] + m[o];
-        const float z = co_unkey(ans) + 0.0f;                // -0 -> +0
-        const float xv = co_unkey(centre[o]);
+        const float z = prc_key_value(ans) + 0.0f;                // -0 -> +0
+        const float xv = prc_key_value(centre[o]);
         const float cr = plain ? xv / z : (xv / mean_abs) / (z + 1e-10f);
         out[at + o] = use_thresh ? (cr > thresh ? 1.f : 0.f) : cr;
         if (noise) noise[at + o] = z;

@@ -14,6 +14,8 @@
 // travels in the kernel arguments and is held in LDS.  In the "plot" orientation (s = fliplr(data.T)) the transpose goes
 // through an LDS tile: the reads run along W, the 4-byte writes along H.
 #include "common.h"
+#include "order_select.h"
+#include "wave.h"
 
 #include <math.h>
 
@@ -23,7 +25,7 @@ namespace {
 
 constexpr int DT = 1024;            // threads per limits workgroup
 constexpr int DW = DT / PRC_WAVE;   // its wavefronts
-constexpr int NBINS = 2048;         // radix digit of 11 bits
+constexpr int NBINS = PRC_RADIX_BINS;
 constexpr uint32_t NONE = 0xffffffffu;
 
 struct LimitsArgs {
@@ -32,38 +34,6 @@ struct LimitsArgs {
     double t[2];            // its fraction
     double hi_scale;
     double* limits;         // [nframes][2]
-};
-
-// order-preserving keys (-0 taken as +0) and the value of a key, widened to double
-__device__ __forceinline__ uint32_t okey(float v) {
-    uint32_t b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long okey(double v) {
-    unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    if (b == 0x8000000000000000ull) b = 0ull;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(uint32_t k) {
-    return (double)__uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ double key_value(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-template <typename T> struct KeyOf;
-template <> struct KeyOf<float> {
-    typedef uint32_t type;
-    static constexpr int passes = 3;
-    static constexpr int shift(int p) { return p == 0 ? 21 : (p == 1 ? 10 : 0); }
-    static constexpr int width(int p) { return p == 2 ? 10 : 11; }
-};
-template <> struct KeyOf<double> {
-    typedef unsigned long long type;
-    static constexpr int passes = 6;
-    static constexpr int shift(int p) { return p == 5 ? 0 : 53 - 11 * p; }
-    static constexpr int width(int p) { return p == 5 ? 9 : 11; }
 };
 
 struct LimitsLds {
@@ -90,49 +60,9 @@ __device__ __forceinline__ void hist_add(uint32_t* h, uint32_t d) {
     if ((todo >> lane) & 1ull) atomicAdd(&h[d], 1u);
 }
 
-// In histogram h, find the bin holding rank r (0-based, ascending): thread t owns bins 2t, 2t+1.
-// Leaves bin, (count below it), (count in it) in sel[0..2].
-__device__ void resolve_digit(LimitsLds& L, const uint32_t* h, int nb, uint32_t r, uint32_t* sel) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t h0 = 2 * tid < nb ? h[2 * tid] : 0u;
-    const uint32_t h1 = 2 * tid + 1 < nb ? h[2 * tid + 1] : 0u;
-    uint32_t inc = h0 + h1;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)inc, o, PRC_WAVE);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) L.ured[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int q = 0; q < wv; ++q) before += L.ured[q];
-    const uint32_t excl = before + inc - (h0 + h1);
-    if (r >= excl && r < excl + h0) {
-        sel[0] = 2 * tid; sel[1] = excl; sel[2] = h0;
-    } else if (r >= excl + h0 && r < excl + h0 + h1) {
-        sel[0] = 2 * tid + 1; sel[1] = excl + h0; sel[2] = h1;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, PRC_WAVE);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, PRC_WAVE);
-        const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-// numpy's _lerp: every operation rounded on its own
-__device__ __forceinline__ double lerp(double a, double b, double t) {
-    const double d = __dsub_rn(b, a);
-    return t >= 0.5 ? __dsub_rn(b, __dmul_rn(d, __dsub_rn(1.0, t))) : __dadd_rn(a, __dmul_rn(d, t));
-}
-
 template <typename T>
 __global__ __launch_bounds__(DT) void display_limits_kernel(const T* __restrict__ frames, LimitsArgs a) {
-    typedef typename KeyOf<T>::type K;
+    typedef typename PrcKeyOf<T>::type K;
     __shared__ LimitsLds L;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const T* x = frames + (size_t)blockIdx.x * (size_t)a.n;
@@ -140,8 +70,8 @@ __global__ __launch_bounds__(DT) void display_limits_kernel(const T* __restrict_
 
     K prefix[2] = {0, 0}, pmask = 0;
     uint32_t r[2] = {a.k[0], a.k[1]}, less[2] = {0u, 0u}, eq[2] = {0u, 0u};
-    for (int p = 0; p < KeyOf<T>::passes; ++p) {
-        const int shift = KeyOf<T>::shift(p), nb = 1 << KeyOf<T>::width(p);
+    for (int p = 0; p < PrcKeyOf<T>::passes; ++p) {
+        const int shift = PrcKeyOf<T>::shift(p), nb = 1 << PrcKeyOf<T>::width(p);
         const uint32_t dm = (uint32_t)nb - 1u;
         for (int b = tid; b < 2 * NBINS; b += DT) (&L.hist[0][0])[b] = 0u;
         if (p == 0 && tid == 0) L.nan = 0u;
@@ -153,7 +83,7 @@ __global__ __launch_bounds__(DT) void display_limits_kernel(const T* __restrict_
             if (i < a.n) {
                 const T v = x[i];
                 if (p == 0 && v != v) L.nan = 1u;
-                const K key = okey(v);
+                const K key = prc_okey(v);
                 const uint32_t digit = (uint32_t)(key >> shift) & dm;
                 if ((key & pmask) == prefix[0]) d0 = digit;
                 if (!same && (key & pmask) == prefix[1]) d1 = digit;
@@ -166,8 +96,8 @@ __global__ __launch_bounds__(DT) void display_limits_kernel(const T* __restrict_
             if (tid == 0) { out[0] = __longlong_as_double(0x7ff8000000000000ll); out[1] = out[0]; }
             return;
         }
-        resolve_digit(L, L.hist[0], nb, r[0], L.sel[0]);
-        resolve_digit(L, same ? L.hist[0] : L.hist[1], nb, r[1], L.sel[1]);
+        prc_resolve_digit(L.hist[0], nb, r[0], L.ured, L.sel[0]);
+        prc_resolve_digit(same ? L.hist[0] : L.hist[1], nb, r[1], L.ured, L.sel[1]);
         for (int j = 0; j < 2; ++j) {
             const uint32_t bin = L.sel[j][0], bef = L.sel[j][1];
             eq[j] = L.sel[j][2];
@@ -187,12 +117,12 @@ __global__ __launch_bounds__(DT) void display_limits_kernel(const T* __restrict_
         const K top = ~(K)0;
         K m0 = top, m1 = top;
         for (uint32_t i = tid; i < a.n; i += DT) {
-            const K key = okey(x[i]);
+            const K key = prc_okey(x[i]);
             if (key > prefix[0] && key < m0) m0 = key;
             if (key > prefix[1] && key < m1) m1 = key;
         }
-        m0 = (K)wave_min_u64(m0);
-        m1 = (K)wave_min_u64(m1);
+        m0 = (K)wave_min((unsigned long long)m0);
+        m1 = (K)wave_min((unsigned long long)m1);
         if (lane == 0) { L.kred[0][wv] = m0; L.kred[1][wv] = m1; }
         __syncthreads();
         if (tid == 0) {
@@ -204,25 +134,10 @@ __global__ __launch_bounds__(DT) void display_limits_kernel(const T* __restrict_
         }
     }
     if (tid == 0) {
-        const double lo = lerp(key_value(prefix[0]), key_value(succ[0]), a.t[0]);
-        const double hi = lerp(key_value(prefix[1]), key_value(succ[1]), a.t[1]);
+        const double lo = prc_np_lerp((double)prc_key_value(prefix[0]), (double)prc_key_value(succ[0]), a.t[0]);
+        const double hi = prc_np_lerp((double)prc_key_value(prefix[1]), (double)prc_key_value(succ[1]), a.t[1]);
         out[0] = lo;
         out[1] = __dmul_rn(a.hi_scale, hi);
-    }
-}
-
-// numpy's linear percentile: q = p / 100, virtual index (n-1) q, its floor and fraction; at or above the last index both
-// order statistics are the last one (the form of prc_track_plan_create)
-void percentile_rank(double p, uint32_t n, uint32_t* k, double* t) {
-    const double q = p / 100.0;
-    const double vi = (double)(n - 1) * q;
-    if (vi >= (double)(n - 1)) {
-        *k = n - 1;
-        *t = 0.0;
-    } else {
-        const double fl = floor(vi);
-        *k = (uint32_t)fl;
-        *t = vi - fl;
     }
 }
 
@@ -336,8 +251,8 @@ extern "C" int prc_display_limits(const void* frames, int32_t dtype, int64_t fra
     if (nframes == 0) return PRC_OK;
     LimitsArgs a;
     a.n = (uint32_t)frame_elems;
-    percentile_rank(p_lo, a.n, &a.k[0], &a.t[0]);
-    percentile_rank(p_hi, a.n, &a.k[1], &a.t[1]);
+    prc_percentile_rank(p_lo, a.n, &a.k[0], &a.t[0]);
+    prc_percentile_rank(p_hi, a.n, &a.k[1], &a.t[1]);
     a.hi_scale = hi_scale;
     a.limits = limits;
     hipStream_t st = (hipStream_t)stream;

@@ -39,6 +39,7 @@
 // contiguous run of elements, its state in a caller-provided device workspace (prc_gal_workspace_bytes), two workgroup
 // barriers per step (block scan, block reduction).  A fallback that takes any D, not a fast path.
 #include "common.h"
+#include "wave.h"
 
 struct GalArgs {
     const float2* ref;
@@ -51,18 +52,6 @@ struct GalArgs {
     float mu1, mu2;
 };
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// DPP moves (the same encodings as nlms.hip)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_src(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROW_MASK, 0xF, false));
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-
 // inclusive scan over the 64 lanes: Hillis-Steele inside each 16-lane row (row_shr 1, 2, 4, 8; lanes without a source add
 // 0), then row_bcast:15 adds row 0's total into row 1 and row 2's into row 3, row_bcast:31 adds rows 0-1 into rows 2-3
 __device__ __forceinline__ void gal_wave_scan2(float& a, float& b) {
@@ -72,28 +61,6 @@ __device__ __forceinline__ void gal_wave_scan2(float& a, float& b) {
     a += dpp_add_src<0x118, 0xF>(a); b += dpp_add_src<0x118, 0xF>(b);
     a += dpp_add_src<0x142, 0xA>(a); b += dpp_add_src<0x142, 0xA>(b);
     a += dpp_add_src<0x143, 0xC>(a); b += dpp_add_src<0x143, 0xC>(b);
-}
-
-// h^H b (yr, yi) and b^H b (bb) summed over the wavefront in one pass: v_permlane32_swap folds the halves (re partials in
-// lanes 0-31, im in 32-63; bb in both), the two chains share four DPP row-sum steps and one row_bcast:15, and lanes 31 / 63
-// are read back
-__device__ __forceinline__ void gal_wave_allsum3(float& yr, float& yi, float& bb) {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_int(yr), __float_as_int(yi), false, false);
-    const auto sb = __builtin_amdgcn_permlane32_swap(__float_as_int(bb), __float_as_int(bb), false, false);
-    float v = __int_as_float(sw[0]) + __int_as_float(sw[1]);
-    float w = __int_as_float(sb[0]) + __int_as_float(sb[1]);
-    v += dpp_mov<0xB1>(v); w += dpp_mov<0xB1>(w);        // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v); w += dpp_mov<0x4E>(w);        // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v); w += dpp_mov<0x141>(w);      // row_half_mirror
-    v += dpp_mov<0x140>(v); w += dpp_mov<0x140>(w);      // row_mirror
-    v += dpp_add_src<0x142, 0xA>(v); w += dpp_add_src<0x142, 0xA>(w);
-    yr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
-    yi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-    bb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), 31));
-}
-
-__device__ __forceinline__ float gal_readlane(float v, int j) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
 }
 
 // mu1 <- min(0.999 mu1 + 1e-8 e^2, 5e-3), complex64 arithmetic; NumPy orders complex numbers lexicographically, so the cap
@@ -133,20 +100,16 @@ __device__ __forceinline__ void gal_element(v2f& b, v2f& k, float& P, v2f bp, v2
     fm = f1;
 }
 
-// lane l <- lane l-1 of src; lane 0 <- `lane0` (the last lane of the row below)
-__device__ __forceinline__ float gal_shr1_from(float lane0, float src) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(src), 0x138, 0xF, 0xF, false));
-}
 // the row's elements moved up by one: element (t, l) <- (t, l-1), (t, 0) <- (t-1, 63); row 0's lane 0 gets 0
 // (t is a constant of the unrolled row loops, so every index below is one)
 template <int N>
 __device__ __forceinline__ v2f gal_shift_row(const v2f (&b)[N], const int t) {
     float o_r = 0.f, o_i = 0.f;
     if (t > 0) {
-        o_r = gal_readlane(b[t > 0 ? t - 1 : 0].x, 63);
-        o_i = gal_readlane(b[t > 0 ? t - 1 : 0].y, 63);
+        o_r = wave_readlane(b[t > 0 ? t - 1 : 0].x, 63);
+        o_i = wave_readlane(b[t > 0 ? t - 1 : 0].y, 63);
     }
-    return v2f{gal_shr1_from(o_r, b[t].x), gal_shr1_from(o_i, b[t].y)};
+    return v2f{wave_shr1(o_r, b[t].x), wave_shr1(o_i, b[t].y)};
 }
 
 // The row form, L <= 64: element m = 64 t + lane lives in row t of lane `lane`.  Row 0 holds the whole lattice (k, P); the
@@ -193,8 +156,8 @@ __global__ __launch_bounds__(64 * MAXW) void gal_row_kernel(GalArgs a) {
         const int cnt = nsteps - n0 < 64 ? (int)(nsteps - n0) : 64;
         float eor = 0.f, eoi = 0.f;
         for (int j = 0; j < cnt; ++j) {
-            const float x_r = gal_readlane(xv.x, j), x_i = gal_readlane(xv.y, j);
-            const float d_r = gal_readlane(dv.x, j), d_i = gal_readlane(dv.y, j);
+            const float x_r = wave_readlane(xv.x, j), x_i = wave_readlane(xv.y, j);
+            const float d_r = wave_readlane(dv.x, j), d_i = wave_readlane(dv.y, j);
             // 1. lattice rows, upwards: bo[m-1], c = conj(k) bo[m-1], the row's inclusive scan plus the rows below -> f[m]
             v2f bpl[LR], fl[LR];
             float car_r = 0.f, car_i = 0.f;
@@ -205,8 +168,8 @@ __global__ __launch_bounds__(64 * MAXW) void gal_row_kernel(GalArgs a) {
                     float cr = k[t].x * bp.x + k[t].y * bp.y, ci = k[t].x * bp.y - k[t].y * bp.x;
                     gal_wave_scan2(cr, ci);
                     fl[t] = v2f{x_r - (car_r + cr), x_i - (car_i + ci)};
-                    car_r += gal_readlane(cr, 63);
-                    car_i += gal_readlane(ci, 63);
+                    car_r += wave_readlane(cr, 63);
+                    car_i += wave_readlane(ci, 63);
                     bpl[t] = bp;
                 }
             }
@@ -229,7 +192,7 @@ __global__ __launch_bounds__(64 * MAXW) void gal_row_kernel(GalArgs a) {
                 bb += b[t].x * b[t].x + b[t].y * b[t].y;
             }
             // 3. one reduction for h^H b and b^H b
-            gal_wave_allsum3(yr, yi, bb);
+            wave_allsum3(yr, yi, bb);
             const float er = d_r - yr, ei = d_i - yi;
             // 4. h += mu2 conj(e) b / (b^H b + 1e-10)
             const float sc = mu2 / (bb + 1e-10f);
@@ -303,10 +266,10 @@ __global__ __launch_bounds__(64 * MAXW) void gal_lattice_kernel(GalArgs a) {
         const int cnt = nsteps - n0 < 64 ? (int)(nsteps - n0) : 64;
         float eor = 0.f, eoi = 0.f;
         for (int j = 0; j < cnt; ++j) {
-            const float x_r = gal_readlane(xv.x, j), x_i = gal_readlane(xv.y, j);
-            const float d_r = gal_readlane(dv.x, j), d_i = gal_readlane(dv.y, j);
+            const float x_r = wave_readlane(xv.x, j), x_i = wave_readlane(xv.y, j);
+            const float d_r = wave_readlane(dv.x, j), d_i = wave_readlane(dv.y, j);
             // 1. the lane's total of c_t = conj(k_t) bo[m-1]
-            const v2f bp0 = {gal_shr1_from(0.f, b[TPL - 1].x), gal_shr1_from(0.f, b[TPL - 1].y)};    // bo of the previous lane's last element
+            const v2f bp0 = {wave_shr1(0.f, b[TPL - 1].x), wave_shr1(0.f, b[TPL - 1].y)};    // bo of the previous lane's last element
             float cr = 0.f, ci = 0.f;
 #pragma unroll
             for (int t = 0; t < TPL; ++t) {
@@ -329,7 +292,7 @@ __global__ __launch_bounds__(64 * MAXW) void gal_lattice_kernel(GalArgs a) {
                 bb += b[t].x * b[t].x + b[t].y * b[t].y;
             }
             // 4. one reduction for h^H b and b^H b
-            gal_wave_allsum3(yr, yi, bb);
+            wave_allsum3(yr, yi, bb);
             const float er = d_r - yr, ei = d_i - yi;
             // 5. h += mu2 conj(e) b / (b^H b + 1e-10)
             const float sc = mu2 / (bb + 1e-10f);
@@ -426,7 +389,7 @@ __global__ __launch_bounds__(GALG_THREADS) void gal_generic_kernel(GalArgs a, un
             yi += hv.x * b.y - hv.y * b.x;
             bb += b.x * b.x + b.y * b.y;
         }
-        gal_wave_allsum3(yr, yi, bb);
+        wave_allsum3(yr, yi, bb);
         if (lane == 0) {
             red_slot[0][wave] = yr;
             red_slot[1][wave] = yi;

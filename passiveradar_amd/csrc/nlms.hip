@@ -23,6 +23,7 @@
 // sample).  The step sizes of a window come from the first wavefront's prepass.  The split is for register space only: at
 // T = 1034 a stream alone steps in 253 ns on one wavefront, 334 on two, 302 on four (tools/nlms_waves_probe.py).
 #include "common.h"
+#include "wave.h"
 #include <vector>
 
 struct NlmsArgs {
@@ -37,20 +38,6 @@ struct NlmsArgs {
     float mu;
 };
 
-// All-lanes sum by DPP (no LDS crossbar): xor-1 / xor-2 inside quads, half-row mirror, row mirror
-// -> every row of 16 lanes holds its row sum; the four row sums are read with v_readlane.
-__device__ __forceinline__ float dpp_f(float x, const int which) {
-    const int i = __float_as_int(x);
-    int r;
-    switch (which) {
-        case 0: r = __builtin_amdgcn_mov_dpp(i, 0xB1, 0xF, 0xF, true); break;    // quad_perm [1,0,3,2]
-        case 1: r = __builtin_amdgcn_mov_dpp(i, 0x4E, 0xF, 0xF, true); break;    // quad_perm [2,3,0,1]
-        case 2: r = __builtin_amdgcn_mov_dpp(i, 0x141, 0xF, 0xF, true); break;   // row_half_mirror
-        default: r = __builtin_amdgcn_mov_dpp(i, 0x140, 0xF, 0xF, true); break;  // row_mirror
-    }
-    return __int_as_float(r);
-}
-typedef float v2f __attribute__((ext_vector_type(2)));
 // acc += conj(w) * u :  (acc.x, acc.y) += w.x (u.x, u.y);  (acc.x, acc.y) += w.y (u.y, -u.x)
 __device__ __forceinline__ void pk_cmac_conj(v2f& acc, v2f w, v2f u) {
     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n"
@@ -76,27 +63,6 @@ __device__ __forceinline__ void pk_cmac_bconj(v2f& w, v2f u, v2f c) {
 __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-}
-
-// Both sums of a step (re, im of conj(w).u) in ONE reduction: v_permlane32_swap puts the real partials of the upper half
-// next to the imaginary partials of the lower half, one add folds the halves, four DPP adds reduce the 16-lane rows (every
-// lane of a row then holds the row sum), row_bcast:15 adds row 0 into row 1 and row 2 into row 3, and lanes 31 / 63 are
-// read back -- 9 instructions where two separate all-lane sums took 22.
-__device__ __forceinline__ void wave_allsum2(float& yr, float& yi) {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_int(yr), __float_as_int(yi), false, false);
-    float v = __int_as_float(sw[0]) + __int_as_float(sw[1]);     // lanes 0-31: re(l) + re(l+32); lanes 32-63: im
-    v += dpp_f(v, 0);
-    v += dpp_f(v, 1);
-    v += dpp_f(v, 2);
-    v += dpp_f(v, 3);
-    // rows 1 and 3 (row_mask 0xA) receive lane 15 of the row before them; rows 0 and 2 add zero
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false));
-    yr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
-    yi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-// lane l <- lane l-1 across the whole wavefront; lane 0 keeps `lane0`
-__device__ __forceinline__ float wave_shr1(float lane0, float src) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(src), 0x138, 0xF, 0xF, false));
 }
 
 // Tap layout (round 3): consecutive taps per lane.  The first A = T - 64 (TPL - 1) lanes hold TPL taps, the others TPL - 1
@@ -192,8 +158,7 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : MAXW)) void nlms_kernel(NlmsArg
                         e0 = fma((double)v.x, (double)v.x, fma((double)v.y, (double)v.y, e0));
                     }
                 }
-#pragma unroll
-                for (int m = 32; m >= 1; m >>= 1) e0 += __shfl_xor(e0, m, 64);
+                e0 = wave_sum(e0);
                 // E(kk) = E(0) + sum_{m < kk} delta(m), delta(m) = |Rw[m + WIN]|^2 - |Rw[m + WIN - T]|^2
                 const int Q = KT >> 6;                 // steps per lane (KT is a multiple of 64)
                 double run = 0.0;
@@ -294,11 +259,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : MAXW)) void nlms_kernel(NlmsArg
 // double and the update.  Two workgroup barriers and ~2 T / 1024 global reads per thread and step: microseconds per step
 // -- a fallback that works at any length, not a fast path.
 #define NLG_THREADS 1024
-__device__ __forceinline__ double nlg_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 __global__ __launch_bounds__(NLG_THREADS) void nlms_generic_kernel(NlmsArgs a, float2* __restrict__ wbuf) {
     __shared__ double red[2][3][NLG_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -321,9 +281,9 @@ __global__ __launch_bounds__(NLG_THREADS) void nlms_generic_kernel(NlmsArgs a, f
             yi += (double)(wv.x * u.y - wv.y * u.x);
             en += (double)u.x * (double)u.x + (double)u.y * (double)u.y;
         }
-        yr = nlg_wave_sum(yr);
-        yi = nlg_wave_sum(yi);
-        en = nlg_wave_sum(en);
+        yr = wave_sum(yr);
+        yi = wave_sum(yi);
+        en = wave_sum(en);
         const int par = (int)(k & 1);                             // two slot sets: a fast wavefront may already write step k + 1's
         if (lane == 0) {
             red[par][0][wave] = yr;

@@ -4,7 +4,7 @@
 // plots_kernel: one 1024-thread workgroup per frame, as track_measure_kernel.  Three lists of C = 2^ceil(log2 max_cells)
 // entries -- A (64-bit), B (64-bit), U (32-bit), 20 C bytes -- sit in LDS up to PRC_PLOTS_LDS_CELLS cells and in the
 // frame's slice of the caller's workspace above (the same code; the global form puts __threadfence before every barrier,
-// as bitonic_desc<Global> of track.hip does, and reads what an atomic of the same phase may have changed with atomic loads).
+// as the sort does (prc_bitonic, order_select.h), and reads what an atomic of the same phase may have changed with atomic loads).
 //   1  stream the frame once (16-byte loads from the first aligned element, scalar head and tail), append the storage
 //      index of every detecting cell to A through an LDS counter;
 //   2  bitonic-sort A ascending: from here on nothing depends on the order of the appends;
@@ -19,6 +19,7 @@
 //   7  one thread per stored plot walks its members once, in ascending storage order, for the float64 sums and the box.
 // Every loop is bounded by the list length or by a strictly decreasing position; no workgroup waits for another.
 #include "common.h"
+#include "order_select.h"
 
 #include <math.h>
 
@@ -43,13 +44,6 @@ struct PlotArgs {
     unsigned char* workspace;  // the global form: 20 C bytes per frame
 };
 
-// order-preserving key of a float (-0 taken as +0), as track.hip
-__device__ __forceinline__ uint32_t fkey(float v) {
-    uint32_t b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // hypotf of a complex64 weight through float64: the squares are exact, one rounding in the sum, the root and the final
 // conversion each -- the correctly rounded |z| except where the last two roundings compound (np.abs of complex64 likewise)
 __device__ __forceinline__ float mag(float re, float im) {
@@ -67,28 +61,6 @@ template <bool Global, class T>
 __device__ __forceinline__ T fresh(const T* p) {
     return Global ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                   : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// bitonic sort of K[0..P) (P a power of two) by the whole workgroup, V (or nullptr) carried along
-template <bool Global, bool Desc>
-__device__ void bitonic(u64* K, uint32_t* V, uint32_t P) {
-    for (u64 k = 2; k <= P; k <<= 1) {
-        for (uint32_t j = (uint32_t)(k >> 1); j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < P; i += PT) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const u64 u = K[i], w = K[l];
-                    const bool first = (i & k) == 0;
-                    const bool swap = Desc ? (first ? (u < w) : (u > w)) : (first ? (u > w) : (u < w));
-                    if (swap) {
-                        K[i] = w; K[l] = u;
-                        if (V) { const uint32_t t = V[i]; V[i] = V[l]; V[l] = t; }
-                    }
-                }
-            }
-            phase_sync<Global>();
-        }
-    }
 }
 
 // first position in K[0..n) whose entry is >= key
@@ -175,7 +147,7 @@ __global__ __launch_bounds__(PT) void plots_kernel(PlotArgs a) {
     while (P < count) P <<= 1;
     for (uint32_t p = count + tid; p < P; p += PT) A[p] = ~0ull;
     phase_sync<Global>();
-    bitonic<Global, false>(A, nullptr, P);
+    prc_bitonic<PT, Global, false>(A, nullptr, P);
 
     // ---- 3: union-find over positions ----
     for (uint32_t p = tid; p < count; p += PT) U[p] = p;
@@ -200,7 +172,7 @@ __global__ __launch_bounds__(PT) void plots_kernel(PlotArgs a) {
     for (uint32_t p = tid; p < P; p += PT)
         B[p] = p < count ? (((u64)(uint32_t)A[find_root<Global>(U, p)] << 32) | (u64)(uint32_t)A[p]) : ~0ull;
     phase_sync<Global>();
-    bitonic<Global, false>(B, nullptr, P);
+    prc_bitonic<PT, Global, false>(B, nullptr, P);
 
     // ---- 5: peak per plot, then the output key at the head's position ----
     for (uint32_t p = tid; p < P; p += PT) { A[p] = 0ull; U[p] = p; }
@@ -209,7 +181,7 @@ __global__ __launch_bounds__(PT) void plots_kernel(PlotArgs a) {
         const u64 m = B[p];
         const uint32_t hp = lower_bound(B, p + 1u, m & 0xffffffff00000000ull);
         const uint32_t i = (uint32_t)m;
-        atomicMax(A + hp, ((u64)fkey(x[i]) << 32) | (u64)(~i));      // the largest stat, then the smallest index
+        atomicMax(A + hp, ((u64)prc_okey(x[i]) << 32) | (u64)(~i));      // the largest stat, then the smallest index
     }
     phase_sync<Global>();
     for (uint32_t p = tid; p < count; p += PT) {
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(PT) void plots_kernel(PlotArgs a) {
     if (tid == 0) a.counts[f] = (int32_t)np;
 
     // ---- 6: output order ----
-    bitonic<Global, true>(A, U, P);
+    prc_bitonic<PT, Global, true>(A, U, P);
 
     // ---- 7: one fixed-order walk per stored plot ----
     const uint32_t m = np < (uint32_t)a.capacity ? np : (uint32_t)a.capacity;

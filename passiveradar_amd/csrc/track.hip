@@ -16,6 +16,8 @@
 // lane-parallel compares and a 64-bit ballot, and removed candidates are masked (one bit each, in LDS), never
 // compacted.  Phase B (Kalman and status updates) runs one lane per track.  fp64 throughout, 2x2 inverses in closed form.
 #include "common.h"
+#include "order_select.h"
+#include "wave.h"
 
 #include <math.h>
 
@@ -23,7 +25,7 @@ namespace {
 
 constexpr int MT = 1024;           // threads per measure workgroup
 constexpr int MW = MT / PRC_WAVE;  // wavefronts per measure workgroup
-constexpr int NBINS = 2048;        // radix digit of 11 bits
+constexpr int NBINS = PRC_RADIX_BINS;
 constexpr int LDS_CAP = 4096;      // candidates sorted in LDS
 constexpr int LDS_ALIVE_CAPACITY = 1 << 19;   // up to here the tracker's alive bits (capacity / 64 words, 64 KiB) sit
                                               // in LDS; above, in a workspace of the plan
@@ -37,16 +39,6 @@ struct MeasureArgs {
     int32_t* counts;
     prc_track_cand* cands;
 };
-
-// order-preserving key of a float (-0 taken as +0) and back
-__device__ __forceinline__ uint32_t fkey(float v) {
-    uint32_t b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float keyf(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // value of storage cell i = h*W + w after the reference's masks (fliplr(frame.T): range row w, Doppler column H-1-h)
 // and its flat index w*H + (H-1-h) in that orientation
@@ -66,15 +58,6 @@ __device__ __forceinline__ Cell cell(const MeasureArgs& a, const float* x, int i
     return r;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, PRC_WAVE);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, PRC_WAVE));
-    return v;
-}
-
 struct MeasureLds {
     uint32_t hist[NBINS];
     unsigned long long keys[LDS_CAP];
@@ -84,54 +67,29 @@ struct MeasureLds {
     uint32_t cnt;
 };
 
-// In the histogram just built, find the bin holding rank r (0-based, ascending): thread t owns bins 2t, 2t+1.
-// Leaves bin, (count below it), (count in it) in L.sel[0..2].
-__device__ void resolve_digit(MeasureLds& L, int nb, uint32_t r) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t h0 = 2 * tid < nb ? L.hist[2 * tid] : 0u;
-    const uint32_t h1 = 2 * tid + 1 < nb ? L.hist[2 * tid + 1] : 0u;
-    uint32_t inc = h0 + h1;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)inc, o, PRC_WAVE);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) L.ured[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int q = 0; q < wv; ++q) before += L.ured[q];
-    const uint32_t excl = before + inc - (h0 + h1);
-    if (r >= excl && r < excl + h0) {
-        L.sel[0] = 2 * tid; L.sel[1] = excl; L.sel[2] = h0;
-    } else if (r >= excl + h0 && r < excl + h0 + h1) {
-        L.sel[0] = 2 * tid + 1; L.sel[1] = excl + h0; L.sel[2] = h1;
-    }
-    __syncthreads();
-}
-
-// The rank-r (0-based, ascending) key among the cells where pred(cell, key) holds, by 11 + 11 + 10 bit digits.
+// The rank-r (0-based, ascending) key among the cells where pred(cell, key) holds, by the digits of PrcKeys32.
 // Returns the key; *less / *eq = how many participating keys lie below / equal it.
 template <class Pred>
 __device__ uint32_t block_select(MeasureLds& L, const MeasureArgs& a, const float* x, uint32_t r, Pred pred,
                                  uint32_t* less, uint32_t* eq) {
-    const int shifts[3] = {21, 10, 0};
-    const int widths[3] = {11, 11, 10};
     uint32_t prefix = 0, pmask = 0, below = 0, in_bin = 0;
-    for (int p = 0; p < 3; ++p) {
-        const uint32_t dm = (1u << widths[p]) - 1u;
+    for (int p = 0; p < PrcKeys32::passes; ++p) {
+        const int shift = PrcKeys32::shift(p), width = PrcKeys32::width(p);
+        const uint32_t dm = (1u << width) - 1u;
         for (int b = threadIdx.x; b < NBINS; b += MT) L.hist[b] = 0u;
         __syncthreads();
         for (int i = threadIdx.x; i < a.n; i += MT) {
             const Cell c = cell(a, x, i);
             uint32_t key;
-            if (pred(c, &key) && (key & pmask) == prefix) atomicAdd(&L.hist[(key >> shifts[p]) & dm], 1u);
+            if (pred(c, &key) && (key & pmask) == prefix) atomicAdd(&L.hist[(key >> shift) & dm], 1u);
         }
         __syncthreads();
-        resolve_digit(L, 1 << widths[p], r);
+        prc_resolve_digit(L.hist, 1 << width, r, L.ured, L.sel);
         const uint32_t bin = L.sel[0], bef = L.sel[1];
         in_bin = L.sel[2];
         __syncthreads();
-        prefix |= bin << shifts[p];
-        pmask |= dm << shifts[p];
+        prefix |= bin << shift;
+        pmask |= dm << shift;
         r -= bef;
         below += bef;
     }
@@ -147,7 +105,7 @@ __device__ __forceinline__ double coord(uint32_t i, uint32_t last, double start,
 
 __device__ __forceinline__ prc_track_cand make_cand(const MeasureArgs& a, unsigned long long key, double mean) {
     const uint32_t idx = (uint32_t)(key & 0xffffffffull);
-    const float v = keyf((uint32_t)(key >> 32));
+    const float v = prc_key_value((uint32_t)(key >> 32));
     const uint32_t r = idx / (uint32_t)a.H, c = idx - r * (uint32_t)a.H;
     prc_track_cand o;
     o.strength = (double)v / mean;
@@ -155,25 +113,6 @@ __device__ __forceinline__ prc_track_cand make_cand(const MeasureArgs& a, unsign
     o.doppler = coord(c, a.H - 1, a.dstart, a.dstep, a.dstop);
     o.index = idx;
     return o;
-}
-
-// bitonic sort, descending, of A[0..P) (P a power of two) by the whole workgroup
-template <bool Global>
-__device__ void bitonic_desc(unsigned long long* A, int P) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += MT) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long u = A[i], w = A[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (u < w) : (u > w)) { A[i] = w; A[l] = u; }
-                }
-            }
-            if (Global) __threadfence();
-            __syncthreads();
-        }
-    }
 }
 
 __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
@@ -199,7 +138,7 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
     }
 
     // ---- threshold: x(k), x(k+1) exactly, then numpy's _lerp ----
-    auto all = [](const Cell& c, uint32_t* key) { *key = fkey(c.v); return true; };
+    auto all = [](const Cell& c, uint32_t* key) { *key = prc_okey(c.v); return true; };
     uint32_t less, eq;
     const uint32_t ka = block_select(L, a, x, a.k, all, &less, &eq);
     const uint32_t k1 = a.k + 1 < (uint32_t)a.n ? a.k + 1 : a.k;
@@ -207,19 +146,18 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
     if (k1 != a.k && less + eq <= k1) {          // x(k+1) is the smallest key above x(k)
         uint32_t m = 0xffffffffu;
         for (int i = tid; i < a.n; i += MT) {
-            const uint32_t key = fkey(cell(a, x, i).v);
+            const uint32_t key = prc_okey(cell(a, x, i).v);
             if (key > ka) m = min(m, key);
         }
-        m = wave_min_u32(m);
+        m = wave_min(m);
         if (lane == 0) L.ured[wv] = m;
         __syncthreads();
         kb = 0xffffffffu;
         for (int q = 0; q < MW; ++q) kb = min(kb, L.ured[q]);
         __syncthreads();
     }
-    const double xa = (double)keyf(ka) / mean, xb = (double)keyf(kb) / mean;
-    const double d = __dsub_rn(xb, xa);
-    const double thr = a.t >= 0.5 ? __dsub_rn(xb, __dmul_rn(d, __dsub_rn(1.0, a.t))) : __dadd_rn(xa, __dmul_rn(d, a.t));
+    const double xa = (double)prc_key_value(ka) / mean, xb = (double)prc_key_value(kb) / mean;
+    const double thr = prc_np_lerp(xa, xb, a.t);
 
     // ---- candidates: count them, keep the first LDS_CAP keys ----
     auto is_cand = [mean, thr](const Cell& c) { return (double)c.v / mean >= thr; };
@@ -227,7 +165,7 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
         const Cell c = cell(a, x, i);
         if (is_cand(c)) {
             const uint32_t pos = atomicAdd(&L.cnt, 1u);
-            if (pos < (uint32_t)LDS_CAP) L.keys[pos] = ((unsigned long long)fkey(c.v) << 32) | c.idx;
+            if (pos < (uint32_t)LDS_CAP) L.keys[pos] = ((unsigned long long)prc_okey(c.v) << 32) | c.idx;
         }
     }
     __syncthreads();
@@ -244,10 +182,10 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
         uint32_t kv = 0, ki = 0;
         if (need_cut) {
             const uint32_t rank = count - m;     // ascending rank of the smallest kept candidate
-            auto cand_key = [&](const Cell& c, uint32_t* key) { *key = fkey(c.v); return is_cand(c); };
+            auto cand_key = [&](const Cell& c, uint32_t* key) { *key = prc_okey(c.v); return is_cand(c); };
             uint32_t lv, ev;
             kv = block_select(L, a, x, rank, cand_key, &lv, &ev);
-            auto tie_idx = [&](const Cell& c, uint32_t* key) { *key = c.idx; return is_cand(c) && fkey(c.v) == kv; };
+            auto tie_idx = [&](const Cell& c, uint32_t* key) { *key = c.idx; return is_cand(c) && prc_okey(c.v) == kv; };
             uint32_t li, ei;
             ki = block_select(L, a, x, rank - lv, tie_idx, &li, &ei);
         }
@@ -257,7 +195,7 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
         for (int i = tid; i < a.n; i += MT) {
             const Cell c = cell(a, x, i);
             if (!is_cand(c)) continue;
-            const uint32_t key = fkey(c.v);
+            const uint32_t key = prc_okey(c.v);
             if (need_cut && !(key > kv || (key == kv && c.idx >= ki))) continue;
             const uint32_t pos = atomicAdd(&L.cnt, 1u);
             if (pos < m) dst[pos] = ((unsigned long long)key << 32) | c.idx;
@@ -270,7 +208,7 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
     if (in_lds) {
         for (int i = (int)m + tid; i < P; i += MT) L.keys[i] = 0ull;   // real keys are > 0: padding sorts last
         __syncthreads();
-        bitonic_desc<false>(L.keys, P);
+        prc_bitonic<MT, false, true>(L.keys, nullptr, (uint32_t)P);
         for (int i = tid; i < (int)m; i += MT) out[i] = make_cand(a, L.keys[i], mean);
         return;
     }
@@ -280,7 +218,7 @@ __global__ __launch_bounds__(MT) void track_measure_kernel(MeasureArgs a) {
     for (int i = (int)m + tid; i < P; i += MT) g[i] = 0ull;
     __threadfence();
     __syncthreads();
-    bitonic_desc<true>(g, P);
+    prc_bitonic<MT, true, true>(g, nullptr, (uint32_t)P);
     for (int base = (((int)m - 1) / MT) * MT; base >= 0; base -= MT) {
         const int i = base + tid;
         const unsigned long long key = i < (int)m ? g[i] : 0ull;
@@ -583,18 +521,7 @@ extern "C" int prc_track_measure(prc_track_plan* plan, const float* frames, int3
     a.W = d.W;
     a.n = d.H * d.W;
     a.capacity = d.capacity;
-    // numpy's linear percentile: q = p / 100, virtual index (n-1) q, its floor and fraction; at or above the last
-    // index both order statistics are the last one
-    const double q = d.percentile / 100.0;
-    const double vi = (double)(a.n - 1) * q;
-    if (vi >= (double)(a.n - 1)) {
-        a.k = (uint32_t)(a.n - 1);
-        a.t = 0.0;
-    } else {
-        const double fl = floor(vi);
-        a.k = (uint32_t)fl;
-        a.t = vi - fl;
-    }
+    prc_percentile_rank(d.percentile, (uint32_t)a.n, &a.k, &a.t);
     // rpts = np.linspace(R, 0, W), dpts = np.linspace(-D, D, H) (:196-197): step = (stop - start) / (num - 1)
     a.rstart = d.range_extent;
     a.rstop = 0.0;
