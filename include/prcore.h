@@ -36,7 +36,7 @@
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
  *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots, tests/test_gpu_tbd_bounds.py prc_tbd and
- *     prc_tbd_trace).
+ *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -53,7 +53,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, fifth edition (additions only, the number stays as for the editions below): prc_tbd_desc, prc_tbd, prc_tbd_trace,
+#define PRC_VERSION 680   /* 680, sixth edition (additions only, the number stays as for the editions below): prc_echo_desc, prc_echo_atom, prc_echo_fit,
+                             prc_echo_cancel_workspace_bytes, prc_echo_cancel (joint least-squares removal of strong echoes at any lag and Doppler);
+                             680, fifth edition (additions only, the number stays as for the editions below): prc_tbd_desc, prc_tbd, prc_tbd_trace,
                              PRC_OPT_TBD_FRAMES, PRC_OPT_TBD_ROWS (track-before-detect: Viterbi integration of a stack of CFAR maps, on device);
                              680, fourth edition (additions only, the number stays as for the editions below): prc_plots_desc, prc_plot_info,
                              prc_plots_workspace_bytes, prc_plots (plot extraction: CFAR detections clustered into plots, on device);
@@ -964,6 +966,74 @@ int prc_xambg_patch(const prc_patch_desc* desc, const void* ref, const void* srv
                     const prc_patch* patches, int32_t npatches, void* out, void* workspace, void* stream);
 int prc_xambg_patch_peaks(const prc_patch_desc* desc, const prc_patch* patches, int32_t npatches, const void* X,
                           prc_patch_peak* peaks, void* stream);
+
+/* ---- joint least-squares removal of strong echoes (CLEAN on the surveillance stream) ------------------------------------ */
+/* A strong moving echo of a noise-like illuminator puts a pedestal 1 / sqrt(B T) below its peak under the whole range-Doppler
+ * surface; this entry point estimates such echoes jointly and subtracts them from the surveillance stream.  For frame b there
+ * are K = counts[b] atoms (lag D_k, Doppler f_k), in the echo convention of prc_xambg_patch (an echo that
+ * prc_xambg_patch_peaks reports at (lag, doppler) is atom (round(lag), doppler)):
+ *   a_k[i] = ref[idx(i - D_k)] exp(+j 2 pi f_k i / sample_rate),  i < n;
+ *   wrap = 1: idx(m) = m mod n (true modulus, negative lags allowed);  wrap = 0: a_k[i] = 0 where i - D_k is outside [0, n);
+ *   ramp = 1 adds the Doppler-slope column s_k[i] = (i / n - 1/2) a_k[i].
+ * Columns A = [a_0, s_0, a_1, s_1, ...], C = (1 + ramp) K of them.  G = A^H A + reg I and g = A^H srv are accumulated in
+ * float64 (the columns themselves are formed in float32), c = G^-1 g by Cholesky in float64.  One refinement (ramp = 1):
+ *   f_k <- f_k + clamp(Im(c_s,k / c_a,k) / (2 pi), +-1/2) sample_rate / n,
+ * skipped for an atom whose c_a is zero or not finite (dead air).  refine = R: R refinements, then the final fit (R + 1 Gram and
+ * solve passes); then out = srv - A c, rounded to complex64.
+ * ref, srv: DEVICE complex64, frame b at element b * frame_stride; out: DEVICE complex64, frame b at b * out_stride;
+ * atoms: DEVICE prc_echo_atom [nframes][max_atoms] with counts: DEVICE int32 [nframes] (the capacity layout of prc_plots: a
+ * detector can write the list on the device); a count outside 0 .. max_atoms is read as clipped; the list is never written.
+ * An atom with |lag| >= n or a Doppler that is not finite is skipped (flag bit 0): the frame is fitted as if it were not listed.
+ * fit: DEVICE prc_echo_fit [nframes][max_atoms], record j for atom j: the refined Doppler, c_a, c_s (0 without ramp) and flags
+ * (bit 0: skipped, bit 1: a refinement was clamped, bit 2: the frame's solve broke down); records from counts[b] on are zero.
+ * info: DEVICE int32 [nframes]: 0, or 1 when a Cholesky pivot was <= 0 -- in float64: not above 2^-40 of its own diagonal entry
+ * of G -- or not finite, or a coefficient was not finite (duplicate atoms, or a silent reference, with reg = 0): that frame's
+ * out = srv, its fits are zero with bit 2 set.  A frame without a valid atom gets out = srv bit for bit.
+ * Every fit record and every info entry is written.
+ * Arithmetic: the phase is exact -- the argument frac(f i0 / sample_rate) of every run of 16 samples is reduced in float64, a
+ * 16-entry table per atom (from float64) covers the run; no float32 ramp over i.  Partial Gram sums go to `workspace`
+ * (prc_echo_cancel_workspace_bytes bytes, DEVICE, 16-byte aligned, not shared by calls in flight) and are added in a fixed
+ * order: no atomics, two calls give the same bits, whatever the workspace held.  3 (refine + 1) + 2 kernels on `stream`;
+ * neither allocates, copies nor synchronises (the call can be captured).  DESIGN.md section 22 has the measured errors.
+ * Memory: frame b of ref / srv is read only inside [b * frame_stride, b * frame_stride + n), the first min(counts[b], max_atoms)
+ * records of frame b's atoms; out is written only inside [b * out_stride, b * out_stride + n).  out must not overlap ref or srv.
+ * PRC_EINVAL: a bad descriptor header, null pointers, n < 1, nframes < 1, frame_stride or out_stride below n with more than one
+ * frame, max_atoms outside 1 .. PRC_ECHO_MAX_ATOMS, refine outside 0 .. PRC_ECHO_MAX_REFINE, wrap or ramp not 0 / 1, refine > 0
+ * with ramp = 0, a negative or non-finite reg, a sample_rate that is zero or not finite, a workspace that is not 16-byte aligned.
+ * PRC_ESHAPE: n >= 2^31 or more than 65535 frames.  prc_echo_cancel_workspace_bytes is host arithmetic and needs no device. */
+#define PRC_ECHO_MAX_ATOMS 32
+#define PRC_ECHO_MAX_REFINE 8
+typedef struct prc_echo_desc {
+    uint32_t struct_size;  /* sizeof(prc_echo_desc) as the host compiled it (see Conventions)              */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int64_t n;             /* samples per frame                                                       */
+    int64_t frame_stride;  /* elements between frames of ref / srv (>= n when nframes > 1)            */
+    int64_t out_stride;    /* elements between frames of out (>= n when nframes > 1)                  */
+    int32_t nframes;       /* frames in the stack                                                     */
+    int32_t max_atoms;     /* 1 .. PRC_ECHO_MAX_ATOMS records per frame in atoms / fit                */
+    int32_t wrap;          /* 1: circular lags, 0: samples outside the frame are zero                 */
+    int32_t ramp;          /* 1: a Doppler-slope column beside every atom                             */
+    int32_t refine;        /* 0 .. PRC_ECHO_MAX_REFINE Doppler refinements before the final fit (needs ramp) */
+    int32_t reserved;      /* 0                                                                       */
+    double sample_rate;    /* Hz                                                                      */
+    double reg;            /* >= 0, added to the diagonal of G                                        */
+} prc_echo_desc;
+#define PRC_ECHO_DESC_SIZE_MIN 72u
+typedef struct prc_echo_atom {   /* 16 bytes */
+    int32_t lag;           /* samples, |lag| < n                                                      */
+    int32_t reserved;
+    double doppler;        /* Hz                                                                      */
+} prc_echo_atom;
+typedef struct prc_echo_fit {    /* 48 bytes */
+    double doppler;        /* Hz, after the refinements                                               */
+    double amp[2];         /* c_a (re, im)                                                            */
+    double slope[2];       /* c_s (re, im); 0 without ramp                                            */
+    uint32_t flags;        /* bit 0: skipped, bit 1: a refinement was clamped, bit 2: the solve broke down */
+    uint32_t reserved;
+} prc_echo_fit;
+int prc_echo_cancel_workspace_bytes(const prc_echo_desc* desc, size_t* bytes);
+int prc_echo_cancel(const prc_echo_desc* desc, const void* ref, const void* srv, const prc_echo_atom* atoms, const int32_t* counts,
+                    void* out, prc_echo_fit* fit, int32_t* info, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

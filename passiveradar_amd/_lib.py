@@ -180,6 +180,28 @@ TBD_FRAMES, TBD_FRAMES_MAX = 8, 32      # PRC_TBD_FRAMES, PRC_TBD_FRAMES_MAX: fr
 TBD_LDS_BYTES = 159744                  # PRC_TBD_LDS_BYTES
 TBD_NONE = 255                          # the back pointer of a cell without a predecessor
 
+class EchoDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("n", C.c_int64), ("frame_stride", C.c_int64), ("out_stride", C.c_int64), ("nframes", C.c_int32),
+                ("max_atoms", C.c_int32), ("wrap", C.c_int32), ("ramp", C.c_int32), ("refine", C.c_int32), ("reserved", C.c_int32),
+                ("sample_rate", C.c_double), ("reg", C.c_double)]
+
+
+class EchoAtom(C.Structure):
+    _fields_ = [("lag", C.c_int32), ("reserved", C.c_int32), ("doppler", C.c_double)]
+
+
+class EchoFit(C.Structure):
+    _fields_ = [("doppler", C.c_double), ("amp", C.c_double * 2), ("slope", C.c_double * 2), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+# NumPy views of prc_echo_atom / prc_echo_fit (same layout as the ctypes mirrors)
+ECHO_ATOM_DTYPE = np.dtype([("lag", "<i4"), ("reserved", "<i4"), ("doppler", "<f8")])
+ECHO_FIT_DTYPE = np.dtype([("doppler", "<f8"), ("amp", "<c16"), ("slope", "<c16"), ("flags", "<u4"), ("reserved", "<u4")])
+ECHO_MAX_ATOMS, ECHO_MAX_REFINE = 32, 8                    # PRC_ECHO_MAX_ATOMS, PRC_ECHO_MAX_REFINE
+ECHO_SKIPPED, ECHO_CLAMPED, ECHO_BROKE_DOWN = 1, 2, 4      # prc_echo_fit.flags
+
 FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
 
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
@@ -309,6 +331,9 @@ _SIGNATURES = {
     "prc_xambg_patch": (C.c_int, [C.POINTER(PatchDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "prc_xambg_patch_peaks": (C.c_int, [C.POINTER(PatchDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "prc_echo_cancel_workspace_bytes": (C.c_int, [C.POINTER(EchoDesc), C.POINTER(C.c_size_t)]),
+    "prc_echo_cancel": (C.c_int, [C.POINTER(EchoDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prc_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32]),
     "prc_comm_destroy": (C.c_int, [C.c_void_p]),

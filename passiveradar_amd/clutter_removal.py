@@ -6,6 +6,7 @@ mismatched inputs; the arithmetic runs in libprcore.so (complex64 streams, compl
 on device).  LS_Filter_SVD is the truncated-SVD form through the float64 Gram matrix of the circulant
 data matrix (csrc/ls_svd.hip); it adds a relative cut ``rcond`` to the reference's absolute one.
 ECA_Filter is not in the reference: LS_Filter_Multiple's bins solved jointly instead of one after another (csrc/eca.hip).
+Nor is cancel_echoes: the joint least-squares removal of strong echoes at any (lag, Doppler) (csrc/echo.hip).
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import numpy as np
 from . import _lib, engine
 
 __all__ = ["LS_Filter", "LS_Filter_SVD", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "ECA_Filter", "NLMS_filter", "GAL_JPE",
-           "set_default_ls_method"]
+           "cancel_echoes", "set_default_ls_method"]
 
 _LS_METHOD = {"m": 0}     # 0 auto | 1 time-domain kernels | 2 FFT kernels (tests flip it)
 
@@ -158,6 +159,107 @@ def ECA_Filter(refChannel, srvChannel, filterLen, sampleRate, dopplerBins=[0], p
     if return_filter:
         return out, d_taps.download((B, T), np.complex128)
     return out
+
+
+def _echo_lists(lags, dopplers, nframes, n, stacked):
+    """HOST prc_echo_atom records [nframes, max_atoms] and counts from per-frame lists, validated as the header asks of a
+    host-built list: ValueError for lags that are not whole samples, |lag| >= n or a Doppler that is not finite"""
+    if not stacked:
+        lags, dopplers = [lags], [dopplers]
+    if len(lags) != nframes or len(dopplers) != nframes:
+        raise ValueError(f"a stack of {nframes} frames takes {nframes} lists of lags and of dopplers")
+    per = []
+    for l, f in zip(lags, dopplers):
+        l = np.atleast_1d(np.asarray(l))
+        f = np.atleast_1d(np.asarray(f, dtype=np.float64))
+        if l.ndim != 1 or l.shape != f.shape:
+            raise ValueError("lags and dopplers must be one-dimensional and of the same length")
+        if l.size and not np.all(l == np.rint(l)):
+            raise ValueError("echo lags are whole samples")
+        l = l.astype(np.int64)
+        if np.any(np.abs(l) >= n):
+            raise ValueError(f"echo lag outside (-{n}, {n})")
+        if not np.all(np.isfinite(f)):
+            raise ValueError("echo Dopplers must be finite")
+        per.append((l, f))
+    M = max(l.size for l, _ in per)
+    rec = np.zeros((nframes, max(M, 1)), dtype=_lib.ECHO_ATOM_DTYPE)
+    counts = np.zeros(nframes, np.int32)
+    for b, (l, f) in enumerate(per):
+        rec["lag"][b, :l.size], rec["doppler"][b, :l.size], counts[b] = l, f, l.size
+    return rec, counts, M
+
+
+def cancel_echoes(refChannel, srvChannel, sampleRate, lags, dopplers, *, ramp=True, refine=2, reg=0.0, wrap=False,
+                  return_fit=False):
+    """Joint least-squares removal of strong echoes from the surveillance stream (CLEAN; prc_echo_cancel of include/prcore.h,
+    csrc/echo.hip).  A strong moving echo of a noise-like illuminator lifts the whole range-Doppler surface by 1 / sqrt(B T)
+    of its peak; the LS cancellers only reach low Doppler and short delay.  Atom k is ref delayed by ``lags[k]`` whole samples
+    and shifted by ``dopplers[k]`` Hz -- an echo that refine_peaks reports at (lag, doppler) is atom (round(lag), doppler).
+    All atoms are fitted at once in float64 normal equations.  ``ramp``: a Doppler-slope column (i/n - 1/2) a_k beside every
+    atom, which absorbs a Doppler error of a fraction of a cell; ``refine``: Gauss-Newton updates of the Dopplers from the
+    slope amplitudes before the final fit (needs ramp; from whole cells one update reaches the noise floor).  ``reg`` >= 0 is
+    added to the diagonal.  ``wrap``: circular delays (fast_xambg's convention) instead of zeros from outside the frame.
+
+    Channels are 1-D, or [nframes, n] stacks with per-frame lists ``lags`` / ``dopplers``; NumPy arrays (staged) or torch
+    device tensors (zero copy, torch's current stream).  Returns the cleaned stream, complex64, of the same kind and shape;
+    with ``return_fit`` also the refined Dopplers, the complex128 amplitudes and slopes and the flags (host arrays; lists of
+    them for a stack).  At most 32 atoms per frame.  Duplicate atoms or a silent reference with reg = 0 break the solve down and
+    raise PrcoreError (reading that costs one small device-to-host copy).  Empty lists return srvChannel."""
+    _check_same(refChannel, srvChannel)
+    if len(refChannel.shape) not in (1, 2):
+        raise ValueError("cancel_echoes takes one-dimensional channels or [nframes, n] stacks")
+    stacked = len(refChannel.shape) == 2
+    n = int(refChannel.shape[-1])
+    nframes = int(refChannel.shape[0]) if stacked else 1
+    if n < 1 or nframes < 1:
+        raise ValueError("cancel_echoes: empty channels")
+    rec, counts, M = _echo_lists(lags, dopplers, nframes, n, stacked)
+    if M == 0:
+        return srvChannel
+    desc = engine.echo_desc(n, sampleRate, M, nframes, wrap, ramp, refine, reg)      # the option checks: ValueError
+    nws = engine.echo_workspace_bytes(desc)
+    dev = _lib.is_device_tensor(refChannel)
+    fit_bytes = nframes * M * _lib.ECHO_FIT_DTYPE.itemsize
+    if dev:
+        import torch
+        ref = refChannel.to(torch.complex64).contiguous()
+        srv = srvChannel.to(device=ref.device, dtype=torch.complex64).contiguous()
+        with torch.cuda.device(ref.device):
+            out = torch.empty_like(srv)
+            d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(ref.device)
+            d_cnt = torch.from_numpy(counts).to(ref.device)
+            d_fit = torch.empty(fit_bytes, dtype=torch.uint8, device=ref.device)
+            d_info = torch.empty(nframes, dtype=torch.int32, device=ref.device)
+            ws = torch.empty(nws, dtype=torch.uint8, device=ref.device)
+            engine.echo_execute(desc, ref, srv, d_rec, d_cnt, out, d_fit, d_info, ws, _lib.torch_stream_ptr(ref.device))
+            info = d_info.cpu().numpy()
+            fit = d_fit.cpu().numpy().view(_lib.ECHO_FIT_DTYPE).reshape(nframes, M) if return_fit else None
+    else:
+        ref = np.ascontiguousarray(refChannel, dtype=np.complex64)
+        srv = np.ascontiguousarray(srvChannel, dtype=np.complex64)
+        _lib.require_gpu()
+        st = engine.staging()
+        d_ref, d_srv, d_out = st.get("echo_ref", ref.nbytes), st.get("echo_srv", srv.nbytes), st.get("echo_out", srv.nbytes)
+        d_rec, d_cnt = st.get("echo_rec", rec.nbytes), st.get("echo_cnt", counts.nbytes)
+        d_fit, d_info, d_ws = st.get("echo_fit", fit_bytes), st.get("echo_info", 4 * nframes), st.get("echo_ws", nws)
+        d_ref.upload(ref)
+        d_srv.upload(srv)
+        d_rec.upload(rec.view(np.uint8))
+        d_cnt.upload(counts)
+        engine.echo_execute(desc, d_ref, d_srv, d_rec, d_cnt, d_out, d_fit, d_info, d_ws)
+        info = d_info.download((nframes,), np.int32)
+        out = d_out.download(srv.shape, np.complex64)
+        fit = d_fit.download((nframes, M), _lib.ECHO_FIT_DTYPE) if return_fit else None
+    if info.any():
+        raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, "cancel_echoes: the Cholesky factorisation broke down (singular normal "
+                               "equations: duplicate atoms or a silent reference); pass reg > 0")
+    if not return_fit:
+        return out
+    per = [tuple(np.array(fit[b, :counts[b]][k]) for k in ("doppler", "amp", "slope", "flags")) for b in range(nframes)]
+    if not stacked:
+        return (out,) + per[0]
+    return (out,) + tuple([p[i] for p in per] for i in range(4))
 
 
 def NLMS_filter(refChannel, srvChannel, filterLen, mu, peek=10, initialTaps=None, returnFilter=False):

@@ -12,6 +12,11 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, PRC_WAVE);
     return v;
 }
+// the sum over the lanes that agree modulo `m` (a power of two below 64): the butterflies 32 down to m
+__device__ __forceinline__ double wave_sum_mod(double v, int m) {
+    for (int o = 32; o >= m; o >>= 1) v += __shfl_xor(v, o, PRC_WAVE);
+    return v;
+}
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, PRC_WAVE));
     return v;

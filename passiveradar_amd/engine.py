@@ -412,6 +412,33 @@ def patch_list(lags, dopplers, frame=None, nframes=1, n=None):
     return rec
 
 
+def echo_desc(n, sample_rate, max_atoms, nframes=1, wrap=False, ramp=True, refine=2, reg=0.0, frame_stride=None, out_stride=None):
+    """prc_echo_desc of include/prcore.h, validated on the host (ValueError) before a device is touched"""
+    d = _lib.EchoDesc()
+    d.n, d.nframes, d.max_atoms = int(n), int(nframes), int(max_atoms)
+    d.frame_stride = int(n if frame_stride is None else frame_stride)
+    d.out_stride = int(n if out_stride is None else out_stride)
+    d.wrap, d.ramp, d.refine = int(bool(wrap)), int(bool(ramp)), int(refine)
+    d.sample_rate, d.reg = float(sample_rate), float(reg)
+    echo_workspace_bytes(d)
+    return d
+
+
+def echo_workspace_bytes(desc):
+    """device bytes prc_echo_cancel needs in ``workspace``; every descriptor check of prc_echo_cancel (host arithmetic)"""
+    nb = C.c_size_t(0)
+    check(lib().prc_echo_cancel_workspace_bytes(C.byref(desc), C.byref(nb)))
+    return int(nb.value)
+
+
+def echo_execute(desc, ref, srv, atoms, counts, out, fit, info, workspace, stream=None):
+    """joint least-squares removal of the listed echoes (device buffers or torch tensors; ``atoms``: DEVICE prc_echo_atom
+    [nframes][max_atoms], ``counts``: int32 [nframes], ``fit``: DEVICE prc_echo_fit records, ``info``: int32 [nframes]).
+    Neither allocates nor synchronises."""
+    check(lib().prc_echo_cancel(C.byref(desc), _ptr(ref), _ptr(srv), _ptr(atoms), _ptr(counts), _ptr(out), _ptr(fit), _ptr(info),
+                                _ptr(workspace), stream))
+
+
 def cfar_training_cells(fw, gw):
     """training cells of CFAR_2D's (fw, gw) window: fw^2 - (e2 - e1)^2 (prc_cfar_training_cells; host arithmetic)"""
     n = C.c_int32(0)

@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib, engine
 
 __all__ = ["fast_xambg", "fast_xambg_multi", "direct_xambg", "caf_plan_for", "set_default_methods", "xambg_patch",
-           "patch_origins"]
+           "patch_origins", "clean_xambg"]
 
 # Kernel selection used by fast_xambg (0 = let the plan decide).  Not part of the reference
 # signature; tests flip it to run the same cases through every kernel family.
@@ -308,3 +308,90 @@ def xambg_patch(refChannel, srvChannel, sampleRate, lags, dopplers, nlags=16, nd
         d_win.upload(window)
     engine.xambg_patch_execute(desc, d_ref, d_srv, d_win, d_rec, npatches, d_out, d_ws)
     return d_out.download((npatches, ndoppler, nlags), np.complex64)
+
+
+# the records clean_xambg returns: one per atom it removed
+ECHO_RECORD_DTYPE = np.dtype([("lag", "<i4"), ("doppler", "<f8"), ("amplitude", "<c16")])
+
+
+def _strongest_cells(mag, npeaks, doppler_guard, half_rows, half_cols):
+    """(rows, cols) of the ``npeaks`` strongest cells of |X| [F, R + 1] outside the +-doppler_guard rows around zero Doppler
+    (row F // 2), one per neighbourhood: a picked cell takes the box of +-half_rows x +-half_cols around it out of the
+    running.  ``mag`` is a NumPy array or a device tensor (then only the picked indices come to the host: one small copy)."""
+    F, W = (int(v) for v in mag.shape)
+    lo, hi = max(F // 2 - doppler_guard, 0), F // 2 + doppler_guard + 1
+    if _lib.is_device_tensor(mag):
+        import torch
+        m = mag.clone()
+        if doppler_guard >= 0:
+            m[lo:hi, :] = -1.0
+        ri, ci = torch.arange(F, device=m.device), torch.arange(W, device=m.device)
+        picked = []
+        for _ in range(int(npeaks)):
+            k = m.argmax()
+            picked.append(k)
+            box = ((ri - k // W).abs() <= half_rows)[:, None] & ((ci - k % W).abs() <= half_cols)[None, :]
+            m.masked_fill_(box, -1.0)
+        picked = torch.stack(picked).cpu().numpy().astype(np.int64)
+        return picked // W, picked % W
+    m = np.array(mag, dtype=np.float32)
+    if doppler_guard >= 0:
+        m[lo:hi, :] = -1.0
+    rows, cols = [], []
+    for _ in range(int(npeaks)):
+        r, c = divmod(int(m.argmax()), W)
+        rows.append(r)
+        cols.append(c)
+        m[max(r - half_rows, 0):r + half_rows + 1, max(c - half_cols, 0):c + half_cols + 1] = -1.0
+    return np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+
+
+def clean_xambg(ref, srv, sampleRate, rangeBins, freqBins, *, npeaks=4, doppler_guard=2, lag_span=0, patch=(16, 16),
+                oversample=4, **cancel_kw):
+    """The range-Doppler surface with its strongest echoes removed from the surveillance stream first (CLEAN): a strong
+    moving echo of a noise-like illuminator lifts the whole surface by 1 / sqrt(B T) of its peak and hides every weaker
+    target under it.  Steps: (1) ``fast_xambg`` of the raw stream; (2) the ``npeaks`` strongest cells outside the
+    +-``doppler_guard`` rows around zero Doppler (what stands there is the cancellers' business; a negative guard keeps every
+    row), one per patch-sized neighbourhood -- this needs one small device-to-host copy, the picked cell indices (the peak
+    records of step 4 and cancel_echoes' breakdown flags and fit are small copies of the same kind: the atom list is built on
+    the host); (3) patches of
+    ``patch`` = (Doppler rows, lags) at 1 / ``oversample`` of a cell, centred on them (``patch_origins``); (4) ``xambg_patch``
+    and ``refine_peaks`` give each echo's lag and sub-cell Doppler; (5) ``cancel_echoes`` fits and subtracts them (``cancel_kw``:
+    ramp, refine, reg, wrap); (6) ``fast_xambg`` of the cleaned stream.  ``lag_span`` = h adds atoms at lags D - h .. D + h
+    around each echo, for oversampled signals whose echoes fall between samples; npeaks (2 h + 1) is at most 32.
+
+    One-dimensional channels, NumPy or torch device tensors.  Returns (surface, echoes): the cleaned surface as fast_xambg
+    returns it, and one ECHO_RECORD_DTYPE record (lag, Doppler in Hz, complex amplitude) per removed atom, on the host, so
+    that a caller can put the removed echoes back into its detections."""
+    from .clutter_removal import cancel_echoes
+    from .target_detection import refine_peaks
+    if len(ref.shape) != 1:
+        raise ValueError("clean_xambg takes one-dimensional channels")
+    npeaks, lag_span, oversample = int(npeaks), int(lag_span), int(oversample)
+    nd, nl = (int(v) for v in patch)
+    if npeaks < 0 or lag_span < 0 or oversample < 1 or nd < 3 or nl < 3:
+        raise ValueError("clean_xambg: npeaks and lag_span are >= 0, oversample >= 1 and a patch has at least 3 x 3 cells")
+    if npeaks * (2 * lag_span + 1) > _lib.ECHO_MAX_ATOMS:
+        raise ValueError(f"clean_xambg: npeaks (2 lag_span + 1) = {npeaks * (2 * lag_span + 1)} atoms, at most {_lib.ECHO_MAX_ATOMS}")
+    n, R, F = int(ref.shape[0]), int(rangeBins), int(freqBins)
+    X = fast_xambg(ref, srv, R, F)
+    if npeaks == 0:
+        return X, np.zeros(0, ECHO_RECORD_DTYPE)
+    mag = X[:, :, 0].abs() if _lib.is_device_tensor(X) else np.abs(X[:, :, 0])
+    rows, cols = _strongest_cells(mag, npeaks, int(doppler_guard), -(-nd // (2 * oversample)), nl // 2)
+    step = float(sampleRate) / n / oversample
+    lags0, dops0 = patch_origins(rows, cols, R, F, n, sampleRate, nl, nd, step)
+    wrap = bool(cancel_kw.get("wrap", False))
+    P = xambg_patch(ref, srv, sampleRate, lags0, dops0, nl, nd, step, wrap=wrap)
+    pk = refine_peaks(P, lags0, dops0, step)
+    if _lib.is_device_tensor(P):
+        pk_lag, pk_dop = pk["lag"].cpu().numpy(), pk["doppler"].cpu().numpy()
+    else:
+        pk_lag, pk_dop = pk["lag"], pk["doppler"]
+    centre = np.rint(pk_lag).astype(np.int64)
+    lags = (centre[:, None] + np.arange(-lag_span, lag_span + 1)[None, :]).reshape(-1)
+    dops = np.repeat(np.asarray(pk_dop, dtype=np.float64), 2 * lag_span + 1)
+    cleaned, f, amp, _, _ = cancel_echoes(ref, srv, sampleRate, lags, dops, return_fit=True, **cancel_kw)
+    rec = np.zeros(lags.shape[0], ECHO_RECORD_DTYPE)
+    rec["lag"], rec["doppler"], rec["amplitude"] = lags, f, amp
+    return fast_xambg(ref, cleaned, R, F), rec
