@@ -24,6 +24,13 @@ except ImportError:
 from passiveradar_amd import clutter_removal as _cr
 _cr.set_default_ls_method(int(os.environ.get("PR_FUZZ_LS_METHOD", "0")))      # e.g. 4: the LS kinds on the 4096-point chain
 KINDS = [int(x) for x in os.environ["PR_FUZZ_KINDS"].split(",")] if os.environ.get("PR_FUZZ_KINDS") else None
+# kinds 26 .. 39 are the kinds of tests/sweep_cases.py (the entry points added after kind 25): random draws of the generators the
+# seeded sweep of tests/test_gpu_sweep.py takes its fixed lists from.  They run only when named in PR_FUZZ_KINDS, so the default
+# draw below stays rng.integers(0, 26) and the seeds of tests/test_gpu_zz_fuzz.py replay the cases they always did.
+sweep_cases = None
+if KINDS and any(k >= 26 for k in KINDS):
+    import sweep_cases
+    sweep_cases.preload()
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 budget = float(sys.argv[2]) if len(sys.argv) > 2 else 90.0
 nthreads = int(sys.argv[3]) if len(sys.argv) > 3 else 1        # dask-style concurrent callers
@@ -47,7 +54,10 @@ def worker(wseed):
   while time.time() - t0 < budget:
       k = rng.integers(0, 26) if KINDS is None else int(rng.choice(KINDS))
       current[wseed] = (int(k), ncase, round(time.time() - t0, 1))          # what this thread is in (printed if it never comes back)
-      if k == 20:     # power-of-two Doppler bin counts: the column-FFT Doppler kernel (256 .. 4096), ragged column tiles
+      if k >= 26:     # a kind of tests/sweep_cases.py: its own oracle and bars, 0 or 1 like the integer kinds
+          name, err, desc = sweep_cases.fuzz_one(k, rng, plain=nthreads > 1)
+          note(name, err, 0.5, desc)
+      elif k == 20:   # power-of-two Doppler bin counts: the column-FFT Doppler kernel (256 .. 4096), ragged column tiles
           F = int(rng.choice([256, 512, 1024, 2048, 4096])); q = int(rng.integers(4, 40)); N = F * q + int(rng.integers(0, F))
           R = int(rng.integers(1, min(700, N // 2 - 1)))
           ref, srv = scene.make_scene(N, 1e5, min(R, 200), int(rng.integers(1 << 30)))
