@@ -460,10 +460,17 @@ def rccl_version():
     return int(v.value) if lib().prc_comm_rccl_version(C.byref(v)) == PRC_OK else None
 
 
+_gpu_seen = False
+
+
 def require_gpu():
-    if device_count() < 1:
-        raise PrcoreError(PRC_EHIP, "no ROCm device visible: " +
-                          lib().prc_last_error().decode("utf-8", "replace"))
+    """raise unless a ROCm device is visible (asked of the runtime until one was seen: it does not go away again)"""
+    global _gpu_seen
+    if not _gpu_seen:
+        if device_count() < 1:
+            raise PrcoreError(PRC_EHIP, "no ROCm device visible: " +
+                              lib().prc_last_error().decode("utf-8", "replace"))
+        _gpu_seen = True
 
 
 class DeviceBuffer:

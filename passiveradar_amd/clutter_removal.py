@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, engine, residence
 
 __all__ = ["LS_Filter", "LS_Filter_SVD", "LS_Filter_Toeplitz", "LS_Filter_Multiple", "ECA_Filter", "NLMS_filter", "GAL_JPE",
            "cancel_echoes", "set_default_ls_method"]
@@ -219,38 +219,21 @@ def cancel_echoes(refChannel, srvChannel, sampleRate, lags, dopplers, *, ramp=Tr
         return srvChannel
     desc = engine.echo_desc(n, sampleRate, M, nframes, wrap, ramp, refine, reg)      # the option checks: ValueError
     nws = engine.echo_workspace_bytes(desc)
-    dev = _lib.is_device_tensor(refChannel)
-    fit_bytes = nframes * M * _lib.ECHO_FIT_DTYPE.itemsize
-    if dev:
-        import torch
-        ref = refChannel.to(torch.complex64).contiguous()
-        srv = srvChannel.to(device=ref.device, dtype=torch.complex64).contiguous()
-        with torch.cuda.device(ref.device):
-            out = torch.empty_like(srv)
-            d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(ref.device)
-            d_cnt = torch.from_numpy(counts).to(ref.device)
-            d_fit = torch.empty(fit_bytes, dtype=torch.uint8, device=ref.device)
-            d_info = torch.empty(nframes, dtype=torch.int32, device=ref.device)
-            ws = torch.empty(nws, dtype=torch.uint8, device=ref.device)
-            engine.echo_execute(desc, ref, srv, d_rec, d_cnt, out, d_fit, d_info, ws, _lib.torch_stream_ptr(ref.device))
-            info = d_info.cpu().numpy()
-            fit = d_fit.cpu().numpy().view(_lib.ECHO_FIT_DTYPE).reshape(nframes, M) if return_fit else None
-    else:
-        ref = np.ascontiguousarray(refChannel, dtype=np.complex64)
-        srv = np.ascontiguousarray(srvChannel, dtype=np.complex64)
-        _lib.require_gpu()
-        st = engine.staging()
-        d_ref, d_srv, d_out = st.get("echo_ref", ref.nbytes), st.get("echo_srv", srv.nbytes), st.get("echo_out", srv.nbytes)
-        d_rec, d_cnt = st.get("echo_rec", rec.nbytes), st.get("echo_cnt", counts.nbytes)
-        d_fit, d_info, d_ws = st.get("echo_fit", fit_bytes), st.get("echo_info", 4 * nframes), st.get("echo_ws", nws)
-        d_ref.upload(ref)
-        d_srv.upload(srv)
-        d_rec.upload(rec.view(np.uint8))
-        d_cnt.upload(counts)
-        engine.echo_execute(desc, d_ref, d_srv, d_rec, d_cnt, d_out, d_fit, d_info, d_ws)
-        info = d_info.download((nframes,), np.int32)
-        out = d_out.download(srv.shape, np.complex64)
-        fit = d_fit.download((nframes, M), _lib.ECHO_FIT_DTYPE) if return_fit else None
+    side = residence.of(refChannel)
+    shape = tuple(srvChannel.shape)
+    ref = side.put("echo_ref", refChannel, np.complex64)
+    srv = side.put("echo_srv", srvChannel, np.complex64)
+    out = side.empty("echo_out", shape, np.complex64)
+    d_rec = side.put("echo_rec", rec.view(np.uint8).reshape(-1), np.uint8)
+    d_cnt = side.put("echo_cnt", counts, np.int32)
+    d_fit = side.scratch("echo_fit", nframes * M * _lib.ECHO_FIT_DTYPE.itemsize)
+    d_info = side.empty("echo_info", (nframes,), np.int32)
+    ws = side.scratch("echo_ws", nws)
+    with side.device():
+        engine.echo_execute(desc, ref, srv, d_rec, d_cnt, out, d_fit, d_info, ws, side.stream)
+        info = side.fetch(d_info, (nframes,), np.int32)
+        out = side.result(out, shape, np.complex64)
+        fit = side.fetch(d_fit, (nframes, M), _lib.ECHO_FIT_DTYPE) if return_fit else None
     if info.any():
         raise _lib.PrcoreError(_lib.PRC_EUNSUPPORTED, "cancel_echoes: the Cholesky factorisation broke down (singular normal "
                                "equations: duplicate atoms or a silent reference); pass reg > 0")

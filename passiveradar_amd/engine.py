@@ -16,10 +16,10 @@ from ._lib import check, lib
 
 
 def _ptr(x):
-    """int / c_void_p / DeviceBuffer / torch tensor -> c_void_p"""
+    """int / c_void_p / DeviceBuffer or another handle of residence.py (``.ptr``) / torch tensor -> c_void_p"""
     if x is None:
         return None
-    if isinstance(x, _lib.DeviceBuffer):
+    if hasattr(x, "ptr"):
         return C.c_void_p(x.ptr)
     if hasattr(x, "data_ptr"):
         return C.c_void_p(x.data_ptr())

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
+from . import _lib, residence
 from ._lib import check, lib
 
 __all__ = ["persistence", "persistence_stack", "gnuplot2_lut", "display_limits", "render_frames", "render_maps"]
@@ -21,9 +21,23 @@ def _weak_scalar(decay):
     return type(decay) in (float, int)
 
 
-def _in_dtype(x_dtype, decay):
+def _in_dtype(x, decay):
     """the device input dtype: float32 only when the reference would form float32 products"""
-    return np.float32 if (x_dtype == np.float32 and _weak_scalar(decay)) else np.float64
+    return np.float32 if (residence.dtype_name(x) == "float32" and _weak_scalar(decay)) else np.float64
+
+
+def _code(dtype):
+    return _lib.REAL_F32 if dtype == np.float32 else _lib.REAL_F64
+
+
+def _stack(X, what):
+    """the side a stack lives on and the stack as [L, H, W]: a torch device tensor [L, H, W] as it is, numpy (H, W, L) as
+    the reference holds it with its last axis moved to the front"""
+    side = residence.of(X, pooled=False)
+    x = X if side.torch else np.asarray(X)
+    if len(x.shape) != 3:
+        raise ValueError(f"{what} takes " + ("a device stack [L, H, W]" if side.torch else "an (H, W, L) stack"))
+    return side, (x if side.torch else np.moveaxis(x, 2, 0))
 
 
 def _check_k(k, hold, L):
@@ -42,37 +56,20 @@ def persistence(X, k, hold, decay):
     torch device tensor [L, H, W], and the result a device [H, W] float64.  k < 0 or hold <= 0 give zeros; otherwise
     k >= L raises IndexError, as the reference's first read X[:, :, k] does."""
     k, hold = int(k), int(hold)
-    if _lib.is_device_tensor(X):
-        import torch
-        if X.dim() != 3:
-            raise ValueError("persistence takes a device stack [L, H, W]")
-        want = torch.float32 if (X.dtype == torch.float32 and _weak_scalar(decay)) else torch.float64
-        x = X.to(want).contiguous()
-        L, H, W = x.shape
-        _check_k(k, hold, L)
-        out = torch.empty((H, W), dtype=torch.float64, device=x.device)
-        code = _lib.REAL_F32 if want == torch.float32 else _lib.REAL_F64
-        with torch.cuda.device(x.device):
-            _run(x.data_ptr(), code, H * W, L, k, 1, hold, decay, out.data_ptr(), _lib.REAL_F64,
-                 _lib.torch_stream_ptr(x.device))
-        return out
-    x = np.asarray(X)
-    if x.ndim != 3:
-        raise ValueError("persistence takes an (H, W, L) stack")
-    H, W, L = x.shape
+    side, x = _stack(X, "persistence")
+    L, H, W = (int(v) for v in x.shape)
     _check_k(k, hold, L)
-    n = max(0, min(k + 1, hold))
-    dt = _in_dtype(x.dtype, decay)
-    f = np.ascontiguousarray(np.moveaxis(x[:, :, k - n + 1:k + 1] if n else x[:, :, :0], 2, 0), dtype=dt)
-    _lib.require_gpu()
-    dx = _lib.DeviceBuffer(f.nbytes)
-    if n:
-        dx.upload(f)
-    do = _lib.DeviceBuffer(H * W * 8)
-    # the n frames read sit at 0 .. n-1; relative to them the frame asked for is n-1 (k < 0 or hold <= 0: none, zeros)
-    _run(dx.ptr, _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64, H * W, n, n - 1, 1, n if n else hold, decay,
-         do.ptr, _lib.REAL_F64, None)
-    return do.download((H, W), np.float64)
+    if not side.torch:
+        # only the n frames the sum reads are uploaded, to 0 .. n-1; relative to them the frame asked for is n-1 (k < 0 or
+        # hold <= 0: none, zeros).  A device stack is resident as it is.
+        n = max(0, min(k + 1, hold))
+        x, L, k, hold = x[k + 1 - n:k + 1] if n else x[:0], n, n - 1, n or hold
+    dt = _in_dtype(x, decay)
+    frames = side.put("frames", x, dt)
+    out = side.empty("out", (H, W), np.float64)
+    with side.device():
+        _run(frames.ptr, _code(dt), H * W, L, k, 1, hold, decay, out.ptr, _lib.REAL_F64, side.stream)
+    return side.result(out, (H, W), np.float64)
 
 
 def persistence_stack(X, hold, decay, out_dtype=np.float64):
@@ -84,36 +81,20 @@ def persistence_stack(X, hold, decay, out_dtype=np.float64):
     f32_out = np.dtype(out_dtype) == np.float32
     if not f32_out and np.dtype(out_dtype) != np.float64:
         raise ValueError("persistence_stack: out_dtype is float64 or float32")
-    if _lib.is_device_tensor(X):
-        import torch
-        if X.dim() != 3:
-            raise ValueError("persistence_stack takes a device stack [L, H, W]")
-        want = torch.float32 if (X.dtype == torch.float32 and _weak_scalar(decay)) else torch.float64
-        x = X.to(want).contiguous()
-        L, H, W = x.shape
-        # a float32 out holds at most PERSISTENCE_TERMS_PER_LAUNCH terms (the launches chain through a float64 out)
-        narrow = f32_out and min(hold, L) > _lib.PERSISTENCE_TERMS_PER_LAUNCH
-        out = torch.empty((L, H, W), dtype=torch.float32 if f32_out and not narrow else torch.float64, device=x.device)
-        code = _lib.REAL_F32 if want == torch.float32 else _lib.REAL_F64
-        with torch.cuda.device(x.device):
-            _run(x.data_ptr(), code, H * W, L, 0, L, hold, decay, out.data_ptr(),
-                 _lib.REAL_F32 if out.dtype == torch.float32 else _lib.REAL_F64, _lib.torch_stream_ptr(x.device))
-        return out.to(torch.float32) if narrow else out
-    x = np.asarray(X)
-    if x.ndim != 3:
-        raise ValueError("persistence_stack takes an (H, W, L) stack")
-    H, W, L = x.shape
-    dt = _in_dtype(x.dtype, decay)
-    f = np.ascontiguousarray(np.moveaxis(x, 2, 0), dtype=dt)
-    _lib.require_gpu()
+    side, x = _stack(X, "persistence_stack")
+    shape = L, H, W = tuple(int(v) for v in x.shape)
+    dt = _in_dtype(x, decay)
+    # a float32 out holds at most PERSISTENCE_TERMS_PER_LAUNCH terms (the launches chain through a float64 out)
     narrow = f32_out and min(hold, L) > _lib.PERSISTENCE_TERMS_PER_LAUNCH
     odt = np.float32 if f32_out and not narrow else np.float64
-    dx = _lib.DeviceBuffer(f.nbytes)
-    dx.upload(f)
-    do = _lib.DeviceBuffer(L * H * W * np.dtype(odt).itemsize)
-    _run(dx.ptr, _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64, H * W, L, 0, L, hold, decay, do.ptr,
-         _lib.REAL_F32 if odt == np.float32 else _lib.REAL_F64, None)
-    out = np.moveaxis(do.download((L, H, W), odt), 0, 2)
+    frames = side.put("frames", x, dt)
+    out = side.empty("out", shape, odt)
+    with side.device():
+        _run(frames.ptr, _code(dt), H * W, L, 0, L, hold, decay, out.ptr, _code(odt), side.stream)
+    out = side.result(out, shape, odt)
+    if side.torch:
+        return out.float() if narrow else out
+    out = np.moveaxis(out, 0, 2)
     return out.astype(np.float32) if narrow else out
 
 
@@ -159,22 +140,19 @@ def _check_frame_shape(H, W):
         raise ValueError(f"frames of {H} x {W}: need H, W >= 1 and H * W < 2^31")
 
 
-def _device_stack(X, what):
-    """a device stack [L, H, W] as contiguous float32 (kept) or float64 (everything else), and its dtype code"""
-    import torch
-    if X.dim() != 3:
-        raise ValueError(f"{what} takes a device stack [L, H, W]")
-    x = (X if X.dtype == torch.float32 else X.to(torch.float64)).contiguous()
-    return x, (_lib.REAL_F32 if x.dtype == torch.float32 else _lib.REAL_F64)
+def _display_dtype(x):
+    """display frames are taken as float32 (kept) or float64 (everything else)"""
+    return np.float32 if residence.dtype_name(x) == "float32" else np.float64
 
 
-def _host_stack(X, what):
-    """a numpy (H, W, L) stack as contiguous [L, H, W], float32 (kept) or float64, and its dtype code"""
-    x = np.asarray(X)
-    if x.ndim != 3:
-        raise ValueError(f"{what} takes an (H, W, L) stack")
-    dt = np.float32 if x.dtype == np.float32 else np.float64
-    return np.ascontiguousarray(np.moveaxis(x, 2, 0), dtype=dt), (_lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64)
+def _limits_arg(side, limits, L):
+    """given limits, (L, 2), host array or tensor, as what ``side`` takes: a tensor as it is for torch, a float64 array
+    otherwise"""
+    if residence.shape(limits) != (L, 2):
+        raise ValueError(f"limits is (L, 2) = ({L}, 2)")
+    if side.torch and hasattr(limits, "data_ptr"):
+        return limits
+    return np.asarray(limits.cpu() if hasattr(limits, "cpu") else limits, dtype=np.float64)
 
 
 def _limits(frames_ptr, code, elems, nframes, p_lo, p_hi, hi_scale, limits_ptr, stream):
@@ -192,28 +170,17 @@ def display_limits(X, p_lo=35, p_hi=99, hi_scale=1.5):
     taken as its values widened to float64).  numpy (H, W, L) gives numpy (L, 2) float64; a torch device tensor
     [L, H, W] gives a device (L, 2) float64 on the tensor's device and torch's current stream."""
     p_lo, p_hi, hi_scale = _check_percentiles(p_lo, p_hi, hi_scale)
-    if _lib.is_device_tensor(X):
-        import torch
-        x, code = _device_stack(X, "display_limits")
-        L, H, W = x.shape
-        _check_frame_shape(H, W)
-        out = torch.empty((L, 2), dtype=torch.float64, device=x.device)
-        if L:
-            with torch.cuda.device(x.device):
-                _limits(x.data_ptr(), code, H * W, L, p_lo, p_hi, hi_scale, out.data_ptr(),
-                        _lib.torch_stream_ptr(x.device))
-        return out
-    f, code = _host_stack(X, "display_limits")
-    L, H, W = f.shape
+    side, x = _stack(X, "display_limits")
+    L, H, W = (int(v) for v in x.shape)
     _check_frame_shape(H, W)
     if L == 0:
-        return np.empty((0, 2), np.float64)
-    _lib.require_gpu()
-    dx = _lib.DeviceBuffer(f.nbytes)
-    dx.upload(f)
-    dl = _lib.DeviceBuffer(L * 16)
-    _limits(dx.ptr, code, H * W, L, p_lo, p_hi, hi_scale, dl.ptr, None)
-    return dl.download((L, 2), np.float64)
+        return side.nothing((0, 2), np.float64)
+    dt = _display_dtype(x)
+    frames = side.put("frames", x, dt)
+    lim = side.empty("limits", (L, 2), np.float64)
+    with side.device():
+        _limits(frames.ptr, _code(dt), H * W, L, p_lo, p_hi, hi_scale, lim.ptr, side.stream)
+    return side.result(lim, (L, 2), np.float64)
 
 
 def render_frames(X, lut=None, limits=None, p_lo=35, p_hi=99, hi_scale=1.5, orient="plot"):
@@ -228,46 +195,23 @@ def render_frames(X, lut=None, limits=None, p_lo=35, p_hi=99, hi_scale=1.5, orie
     p_lo, p_hi, hi_scale = _check_percentiles(p_lo, p_hi, hi_scale)
     lut = _check_lut(lut)
     oc = _check_orient(orient)
-    if _lib.is_device_tensor(X):
-        import torch
-        x, code = _device_stack(X, "render_frames")
-        L, H, W = x.shape
-        _check_frame_shape(H, W)
-        if limits is not None:
-            lim = limits if _lib.is_device_tensor(limits) else torch.from_numpy(np.asarray(limits, dtype=np.float64))
-            if tuple(lim.shape) != (L, 2):
-                raise ValueError(f"limits is (L, 2) = ({L}, 2)")
-            lim = lim.to(device=x.device, dtype=torch.float64).contiguous()
-        out = torch.empty((L, W, H, 4) if oc == _lib.DISPLAY_PLOT else (L, H, W, 4), dtype=torch.uint8, device=x.device)
-        if L:
-            with torch.cuda.device(x.device):
-                st = _lib.torch_stream_ptr(x.device)
-                if limits is None:
-                    lim = torch.empty((L, 2), dtype=torch.float64, device=x.device)
-                    _limits(x.data_ptr(), code, H * W, L, p_lo, p_hi, hi_scale, lim.data_ptr(), st)
-                _rgba(x.data_ptr(), code, H, W, L, lim.data_ptr(), lut, oc, out.data_ptr(), st)
-        return out
-    f, code = _host_stack(X, "render_frames")
-    L, H, W = f.shape
+    side, x = _stack(X, "render_frames")
+    L, H, W = (int(v) for v in x.shape)
     _check_frame_shape(H, W)
     shape = (L, W, H, 4) if oc == _lib.DISPLAY_PLOT else (L, H, W, 4)
     if limits is not None:
-        lim = np.ascontiguousarray(limits.cpu().numpy() if _lib.is_device_tensor(limits) else limits, dtype=np.float64)
-        if lim.shape != (L, 2):
-            raise ValueError(f"limits is (L, 2) = ({L}, 2)")
+        limits = _limits_arg(side, limits, L)
     if L == 0:
-        return np.empty(shape, np.uint8)
-    _lib.require_gpu()
-    dx = _lib.DeviceBuffer(f.nbytes)
-    dx.upload(f)
-    dl = _lib.DeviceBuffer(L * 16)
-    if limits is None:
-        _limits(dx.ptr, code, H * W, L, p_lo, p_hi, hi_scale, dl.ptr, None)
-    else:
-        dl.upload(lim)
-    do = _lib.DeviceBuffer(L * H * W * 4)
-    _rgba(dx.ptr, code, H, W, L, dl.ptr, lut, oc, do.ptr, None)
-    return do.download(shape, np.uint8)
+        return side.nothing(shape, np.uint8)
+    dt = _display_dtype(x)
+    frames = side.put("frames", x, dt)
+    lim = side.empty("limits", (L, 2), np.float64) if limits is None else side.put("limits", limits, np.float64)
+    out = side.empty("out", shape, np.uint8)
+    with side.device():
+        if limits is None:
+            _limits(frames.ptr, _code(dt), H * W, L, p_lo, p_hi, hi_scale, lim.ptr, side.stream)
+        _rgba(frames.ptr, _code(dt), H, W, L, lim.ptr, lut, oc, out.ptr, side.stream)
+    return side.result(out, shape, np.uint8)
 
 
 RENDER_SLAB_BYTES = 1 << 28     # render_maps: float64 persistence frames alive at a time (default slab)
@@ -282,13 +226,13 @@ def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, cfar="mean", 
     RENDER_SLAB_BYTES); a slab reads the ``hold - 1`` CFAR frames before its first one.  Given ``limits`` are (L, 2).
     ``cfar="os"`` puts CFAR_2D_OS (reference scale, rank ``cfar_rank``) in the cell average's place."""
     import torch
-    from .target_detection import _chain_cfar
-    if cfar not in ("mean", "os"):
-        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
+    from .target_detection import _chain_cfar, _check_cfar
+    _check_cfar(cfar)
     hold = int(hold)
     if slab is not None and int(slab) < 1:
         raise ValueError("slab is a number of frames >= 1")
-    if not _lib.is_device_tensor(xambg):
+    side = residence.of(xambg)
+    if not side.torch:
         x = np.asarray(xambg)
         if x.ndim != 3:
             raise ValueError("render_maps takes (H, W, L) maps")
@@ -297,17 +241,17 @@ def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, cfar="mean", 
         return render_maps(torch.from_numpy(x).cuda(), fw, gw, hold, decay, slab, cfar, cfar_rank, **render_kw).cpu().numpy()
     if xambg.dim() != 3:
         raise ValueError("render_maps takes a device stack [L, H, W]")
-    L, H, W = xambg.shape
+    shape = L, H, W = tuple(int(v) for v in xambg.shape)
     _check_frame_shape(H, W)
     limits = render_kw.pop("limits", None)
     if limits is not None:
-        limits = limits if _lib.is_device_tensor(limits) else torch.from_numpy(np.asarray(limits, dtype=np.float64))
-        if tuple(limits.shape) != (L, 2):
-            raise ValueError(f"limits is (L, 2) = ({L}, 2)")
-        limits = limits.to(device=xambg.device, dtype=torch.float64)
+        limits = _limits_arg(side, limits, L)
+        limits = (limits if hasattr(limits, "data_ptr") else torch.from_numpy(limits)).to(device=xambg.device, dtype=torch.float64)
     if L == 0:
         return render_frames(torch.empty((0, H, W), dtype=torch.float64, device=xambg.device), limits=limits, **render_kw)
-    cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
+    cplx = xambg.is_complex()
+    maps = side.put("maps", xambg, np.complex64 if cplx else np.float32)
+    cf = side.result(_chain_cfar(side, maps, shape, cplx, fw, gw, cfar, cfar_rank), shape, np.float32)
     step = int(slab) if slab is not None else max(1, RENDER_SLAB_BYTES // (H * W * 8))
     outs = []
     for s0 in range(0, L, step):
@@ -315,8 +259,8 @@ def render_maps(xambg, fw=18, gw=4, hold=20, decay=0.9, slab=None, cfar="mean", 
         b0 = max(0, s0 - max(hold - 1, 0))                  # the first CFAR frame this slab's sums read
         src = cf[b0:s1].to(torch.float64)                   # the reference's CF is float64: float64 products
         st = torch.empty((s1 - s0, H, W), dtype=torch.float64, device=cf.device)
-        with torch.cuda.device(cf.device):
+        with side.device():
             _run(src.data_ptr(), _lib.REAL_F64, H * W, s1 - b0, s0 - b0, s1 - s0, hold, decay, st.data_ptr(),
-                 _lib.REAL_F64, _lib.torch_stream_ptr(cf.device))
+                 _lib.REAL_F64, side.stream)
         outs.append(render_frames(st, limits=None if limits is None else limits[s0:s1], **render_kw))
     return outs[0] if len(outs) == 1 else torch.cat(outs)

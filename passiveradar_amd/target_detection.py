@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, engine, residence
 from ._lib import check, lib
 
 __all__ = ["CFAR_2D", "CFAR_2D_abs", "CFAR_2D_OS", "cfar_training_cells", "os_cfar_threshold", "get_measurements",
@@ -24,63 +24,49 @@ __all__ = ["CFAR_2D", "CFAR_2D_abs", "CFAR_2D_OS", "cfar_training_cells", "os_cf
            "tbd_maps"]
 
 
+def _map_dtype(cplx):
+    return np.complex64 if cplx else np.float32
+
+
+def _cfar_mean(side, x, shape, cplx, fw, gw, thresh=None):
+    """prc_cfar2d / prc_cfar2d_c64 of the resident frame or stack ``x``: the handle of the float32 map"""
+    frames = 1 if len(shape) == 2 else shape[0]
+    out = side.empty("cfar_o", shape, np.float32)
+    fn = lib().prc_cfar2d_c64 if cplx else lib().prc_cfar2d
+    with side.device():                            # launch on the data's device and, for torch, its current stream there
+        check(fn(x.ptr, shape[-2], shape[-1], int(fw), int(gw), int(thresh is not None), float(thresh or 0.0), out.ptr, frames,
+                 side.stream))
+    return out
+
+
+def _cfar_return(side, r, thresh):
+    """CFAR_2D's return convention for the float32 map ``r``: float64 arrays / float32 tensors, boolean with a threshold"""
+    if side.torch:
+        return r.bool() if thresh is not None else r
+    return r > 0.5 if thresh is not None else r.astype(np.float64)
+
+
 def CFAR_2D(X, fw, gw, thresh=None):
     """Constant false alarm rate filter (same contract as target_detection.py:683-703): X is a 2-D
     (Doppler x range) magnitude map -- or a stack [nframes, H, W] / torch device tensor for batches;
     returns the CFAR ratio in float64 (boolean if ``thresh`` is given), like the reference."""
-    if _lib.is_device_tensor(X):
-        import torch
-        x = X.to(torch.float32).contiguous()
-        frames = 1 if x.dim() == 2 else x.shape[0]
-        H, W = x.shape[-2], x.shape[-1]
-        out = torch.empty_like(x)
-        with torch.cuda.device(x.device):          # launch on the tensor's device and torch's stream there
-            check(lib().prc_cfar2d(x.data_ptr(), H, W, int(fw), int(gw), int(thresh is not None),
-                                   float(thresh or 0.0), out.data_ptr(), frames, _lib.torch_stream_ptr(x.device)))
-        return out.bool() if thresh is not None else out
-    x = np.ascontiguousarray(X, dtype=np.float32)
-    frames = 1 if x.ndim == 2 else x.shape[0]
-    H, W = x.shape[-2], x.shape[-1]
-    st = engine.staging()
-    dx = st.get("cfar_x", x.nbytes)
-    do = st.get("cfar_o", x.nbytes)
-    dx.upload(x)
-    check(lib().prc_cfar2d(dx.ptr, H, W, int(fw), int(gw), int(thresh is not None), float(thresh or 0.0),
-                           do.ptr, frames, None))
-    out = do.download(x.shape, np.float32)
-    return out > 0.5 if thresh is not None else out.astype(np.float64)
+    side = residence.of(X)
+    shape = residence.shape(X)
+    out = _cfar_mean(side, side.put("cfar_x", X, np.float32), shape, False, fw, gw, thresh)
+    return _cfar_return(side, side.result(out, shape, np.float32), thresh)
 
 
 def CFAR_2D_abs(xambg, fw, gw, thresh=None):
     """``CFAR_2D(np.abs(xambg), fw, gw, thresh)`` -- the call of range_doppler_plot.py:56-57 -- in ONE kernel: the
     complex64 range-Doppler map (2-D, a stack [nframes, H, W], or torch device tensors of those shapes) goes in as it
-    is and |X| is taken while the CFAR tiles are loaded, so the complex map is read once and no magnitude map is written.  Same return convention as
-    CFAR_2D."""
-    if _lib.is_device_tensor(xambg):
-        import torch
-        x = xambg.to(torch.complex64).contiguous()
-        if x.dim() not in (2, 3):
-            raise ValueError("CFAR_2D_abs takes a 2-D map or a stack [nframes, H, W]")
-        frames = 1 if x.dim() == 2 else x.shape[0]
-        H, W = x.shape[-2], x.shape[-1]
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib().prc_cfar2d_c64(x.data_ptr(), H, W, int(fw), int(gw), int(thresh is not None),
-                                       float(thresh or 0.0), out.data_ptr(), frames, _lib.torch_stream_ptr(x.device)))
-        return out.bool() if thresh is not None else out
-    x = np.ascontiguousarray(xambg, dtype=np.complex64)
-    if x.ndim not in (2, 3):
+    is and |X| is taken while the CFAR tiles are loaded, so the complex map is read once and no magnitude map is written.
+    Same return convention as CFAR_2D."""
+    side = residence.of(xambg)
+    shape = residence.shape(xambg)
+    if len(shape) not in (2, 3):
         raise ValueError("CFAR_2D_abs takes a 2-D map or a stack [nframes, H, W]")
-    frames = 1 if x.ndim == 2 else x.shape[0]
-    H, W = x.shape[-2], x.shape[-1]
-    st = engine.staging()
-    dx = st.get("cfar_xc", x.nbytes)
-    do = st.get("cfar_o", x.nbytes // 2)
-    dx.upload(x)
-    check(lib().prc_cfar2d_c64(dx.ptr, H, W, int(fw), int(gw), int(thresh is not None), float(thresh or 0.0),
-                               do.ptr, frames, None))
-    out = do.download(x.shape, np.float32)
-    return out > 0.5 if thresh is not None else out.astype(np.float64)
+    out = _cfar_mean(side, side.put("cfar_xc", xambg, np.complex64), shape, True, fw, gw, thresh)
+    return _cfar_return(side, side.result(out, shape, np.float32), thresh)
 
 
 # ---- order-statistic CFAR on CFAR_2D's window (DESIGN.md section 18) ----------------------------------------------------
@@ -122,6 +108,25 @@ def os_cfar_threshold(pfa, ncells, rank, law="magnitude"):
     return float(np.sqrt(T)) if law == "magnitude" else float(T)
 
 
+def _cfar_os_plan(shape, cplx, fw, gw, thresh=None, rank=None, scale="reference"):
+    """prc_cfar_os of a frame or a stack, as far as the host goes: (descriptor, frames, workspace bytes); every argument
+    check (ValueError)"""
+    frames = 1 if len(shape) == 2 else int(shape[0])
+    desc = engine.cfar_os_desc(int(shape[-2]), int(shape[-1]), fw, gw, rank, scale, cplx, thresh)
+    return desc, frames, engine.cfar_os_workspace_bytes(desc, max(frames, 1))
+
+
+def _cfar_os(side, x, shape, plan, want_noise=False):
+    """the resident ``x`` through prc_cfar_os as planned: the handles of the float32 map and of the noise map (or None)"""
+    desc, frames, nws = plan
+    out = side.empty("cfar_o", shape, np.float32)
+    z = side.empty("cfar_z", shape, np.float32) if want_noise else None
+    ws = side.scratch("cfar_ws", nws)
+    with side.device():
+        engine.cfar_os_execute(desc, x, out, z, frames, ws, side.stream)
+    return out, z
+
+
 def CFAR_2D_OS(X, fw, gw, thresh=None, *, rank=None, scale="reference", return_noise=False):
     """Order-statistic CFAR on CFAR_2D's window: the noise estimate z of a cell is the ``rank``-th smallest (1-based,
     default ceil(0.75 Nt)) of its Nt = cfar_training_cells(fw, gw) training cells, selected exactly, instead of their mean
@@ -131,77 +136,52 @@ def CFAR_2D_OS(X, fw, gw, thresh=None, *, rank=None, scale="reference", return_n
     X is a 2-D map or a stack [nframes, H, W], NumPy or a torch device tensor, real or complex (|X| is taken on load, as
     CFAR_2D_abs does).  Returns as CFAR_2D: float64 from NumPy (bool with ``thresh``), float32 / bool tensors on the caller's
     device and stream for torch; with ``return_noise=True`` also the z map (float64 / float32)."""
-    dev = _lib.is_device_tensor(X)
-    if dev:
-        import torch
-        x = X.to(torch.complex64 if X.is_complex() else torch.float32).contiguous()
-        cplx, ndim = x.is_complex(), x.dim()
-    else:
-        x = np.asarray(X)
-        cplx, ndim = np.iscomplexobj(x), x.ndim
-        x = np.ascontiguousarray(x, dtype=np.complex64 if cplx else np.float32)
-    if ndim not in (2, 3):
+    side = residence.of(X)
+    shape = residence.shape(X)
+    if len(shape) not in (2, 3):
         raise ValueError("CFAR_2D_OS takes a 2-D map or a stack [nframes, H, W]")
-    frames = 1 if ndim == 2 else int(x.shape[0])
-    H, W = int(x.shape[-2]), int(x.shape[-1])
-    desc = engine.cfar_os_desc(H, W, fw, gw, rank, scale, cplx, thresh)
-    nws = engine.cfar_os_workspace_bytes(desc, max(frames, 1))     # every argument check, on the host
-    if dev:
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        z = torch.empty_like(out) if return_noise else None
-        ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws else None
-        if frames:
-            with torch.cuda.device(x.device):          # launch on the tensor's device and torch's stream there
-                engine.cfar_os_execute(desc, x, out, z, frames, ws, _lib.torch_stream_ptr(x.device))
-        out = out.bool() if thresh is not None else out
-        return (out, z) if return_noise else out
-    _lib.require_gpu()
-    if frames == 0:
-        out = np.zeros(x.shape, dtype=bool if thresh is not None else np.float64)
-        return (out, np.zeros(x.shape, dtype=np.float64)) if return_noise else out
-    st = engine.staging()
-    nb = frames * H * W * 4
-    dx = st.get("cfar_xc" if cplx else "cfar_x", x.nbytes)
-    do = st.get("cfar_o", nb)
-    dz = st.get("cfar_z", nb) if return_noise else None
-    ws = st.get("cfar_ws", nws) if nws else None
-    dx.upload(x)
-    engine.cfar_os_execute(desc, dx, do, dz, frames, ws)
-    out = do.download(x.shape, np.float32)
-    out = out > 0.5 if thresh is not None else out.astype(np.float64)
-    return (out, dz.download(x.shape, np.float32).astype(np.float64)) if return_noise else out
+    cplx = residence.iscomplex(X)
+    plan = _cfar_os_plan(shape, cplx, fw, gw, thresh, rank, scale)
+    if plan[1] == 0:                               # no frames: nothing to launch, nothing to allocate
+        out = z = side.nothing(shape, np.float32)
+    else:
+        out, z = _cfar_os(side, side.put("cfar_xc" if cplx else "cfar_x", X, _map_dtype(cplx)), shape, plan, return_noise)
+        out, z = side.result(out, shape, np.float32), (side.result(z, shape, np.float32) if return_noise else None)
+    out = _cfar_return(side, out, thresh)
+    if not return_noise:
+        return out
+    return out, (z if side.torch else z.astype(np.float64))
 
 
-def _chain_cfar(x, fw, gw, cfar, cfar_rank, scale="reference"):
-    """the CFAR stage of the device chains on a torch stack: "mean" = CFAR_2D / CFAR_2D_abs, "os" = CFAR_2D_OS (``scale``
-    applies to it alone)"""
-    if cfar == "os":
-        return CFAR_2D_OS(x, fw, gw, rank=cfar_rank, scale=scale)
-    if cfar != "mean":
-        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
-    return CFAR_2D_abs(x, fw, gw) if x.is_complex() else CFAR_2D(x, fw, gw)
-
-
-def _chain_cfar_staged(x, fw, gw, cfar, cfar_rank, scale="reference"):
-    """the same stage for a host stack [nframes, H, W] on buffers the chain owns (null stream): returns
-    (maps buffer, nframes, H, W, what must stay alive: the uploaded input first)"""
+def _check_cfar(cfar):
     if cfar not in ("mean", "os"):
         raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
-    cplx = np.iscomplexobj(x)
-    xs = np.ascontiguousarray(x, dtype=np.complex64 if cplx else np.float32)
-    nframes, H, W = xs.shape
-    dx = _lib.DeviceBuffer(xs.nbytes)
-    dx.upload(xs)
-    do = _lib.DeviceBuffer(nframes * H * W * 4)
-    ws = None
+
+
+def _chain_cfar(side, x, shape, cplx, fw, gw, cfar, cfar_rank, scale="reference"):
+    """the CFAR stage of the chains on the resident stack ``x`` [nframes, H, W]: "mean" = CFAR_2D / CFAR_2D_abs, "os" =
+    CFAR_2D_OS (``scale`` applies to it alone).  Returns the handle of the float32 maps."""
+    _check_cfar(cfar)
     if cfar == "os":
-        desc = engine.cfar_os_desc(H, W, fw, gw, cfar_rank, scale, cplx)
-        ws = _lib.DeviceBuffer(engine.cfar_os_workspace_bytes(desc, nframes))
-        engine.cfar_os_execute(desc, dx, do, None, nframes, ws)
+        return _cfar_os(side, x, shape, _cfar_os_plan(shape, cplx, fw, gw, rank=cfar_rank, scale=scale))[0]
+    return _cfar_mean(side, x, shape, cplx, fw, gw)
+
+
+def _maps_stack(xambg, who, frame_ok=True):
+    """what the chains take, as a stack [N, H, W] with its side and whether it is complex: a torch device tensor [N, H, W]
+    (a frame [H, W] is a stack of one, where ``frame_ok``) or NumPy (H, W, Nframes) as the reference's scripts load it.  A chain holds its
+    stages' buffers itself (not pooled): the front doors it calls use the pool."""
+    side = residence.of(xambg, pooled=False)
+    if side.torch:
+        x = xambg.unsqueeze(0) if frame_ok and xambg.dim() == 2 else xambg
+        if x.dim() != 3:
+            raise ValueError(f"{who} takes a device stack [N, H, W]")
     else:
-        fn = lib().prc_cfar2d_c64 if cplx else lib().prc_cfar2d
-        check(fn(dx.ptr, H, W, int(fw), int(gw), 0, 0.0, do.ptr, nframes, None))
-    return do, nframes, H, W, (dx, ws)
+        x = np.asarray(xambg)
+        if x.ndim != 3:
+            raise ValueError(f"{who} takes (H, W, Nframes) frames")
+        x = np.moveaxis(x, 2, 0)
+    return side, x, residence.iscomplex(x)
 
 
 # ---- multi-target tracker (target_detection.py:164-537) ---------------------------------------------------------------
@@ -261,92 +241,72 @@ def expected_capacity(H, W, percentile=TRACK_PERCENTILE):
     return max(1, n - 1 - k) + 64
 
 
-def _frames_shape(x):
-    if x.ndim == 2:
-        return 1, x.shape[0], x.shape[1]
-    if x.ndim == 3:
-        return x.shape[0], x.shape[1], x.shape[2]
+def _frames_shape(shape):
+    if len(shape) == 2:
+        return 1, int(shape[0]), int(shape[1])
+    if len(shape) == 3:
+        return int(shape[0]), int(shape[1]), int(shape[2])
     raise ValueError("expected a frame [H, W] or a stack [nframes, H, W]")
 
 
 class _Measured:
-    """counts + candidate records of a stack of frames on the device, measured with a plan whose capacity holds every
-    frame's candidates: after one measure the counts are read, and if any exceeds the capacity the plan is rebuilt at
-    the exact maximum and the stack measured again (a deterministic sizing step).  ``capacity`` pins the capacity (no
-    rebuild: frames over it keep their first `capacity` candidates and the tracker flags them); ``start_capacity`` only
-    replaces the first guess (default: expected_capacity)."""
+    """counts + candidate records of a resident stack of frames (``frames``: its handle, float32), measured with a plan whose
+    capacity holds every frame's candidates: after one measure the counts are read, and if any exceeds the capacity the plan
+    is rebuilt at the exact maximum and the stack measured again (a deterministic sizing step).  ``capacity`` pins the
+    capacity (no rebuild: frames over it keep their first `capacity` candidates and the tracker flags them);
+    ``start_capacity`` only replaces the first guess (default: expected_capacity)."""
 
-    def __init__(self, frames_ptr, nframes, H, W, frame_extent, ntracks, alloc, stream, percentile=TRACK_PERCENTILE,
-                 capacity=None, start_capacity=None):
-        self.alloc, self.stream = alloc, stream
-        self.nframes = nframes
+    def __init__(self, side, frames, nframes, H, W, frame_extent, ntracks, percentile=TRACK_PERCENTILE, capacity=None,
+                 start_capacity=None):
+        self.side, self.frames, self.nframes = side, frames, nframes
         self.rebuilt = False
         cap = int(capacity or start_capacity or expected_capacity(H, W, percentile))
-        self.counts_buf = alloc("counts", 4 * max(nframes, 1))
-        for attempt in range(2):
-            self.plan = TrackPlan(H, W, ntracks, cap, frame_extent, percentile)
-            self.cands_buf = alloc("cands", 32 * max(nframes, 1) * cap)
-            self.plan.measure(frames_ptr, nframes, self.counts_buf.ptr, self.cands_buf.ptr, stream)
-            self.counts = self.counts_buf.download(nframes, np.int32, stream=stream)
-            need = int(self.counts.max()) if nframes else 0
-            if need <= cap or capacity:
-                break
-            cap = need
-            self.rebuilt = True
+        with side.device():
+            self.counts_buf = side.scratch("counts", 4 * max(nframes, 1))
+            for attempt in range(2):
+                self.plan = TrackPlan(H, W, ntracks, cap, frame_extent, percentile)
+                self.cands_buf = side.scratch("cands", 32 * max(nframes, 1) * cap)
+                self.plan.measure(frames.ptr, nframes, self.counts_buf.ptr, self.cands_buf.ptr, side.stream)
+                self.counts = side.fetch(self.counts_buf, nframes, np.int32)
+                need = int(self.counts.max()) if nframes else 0
+                if need <= cap or capacity:
+                    break
+                cap = need
+                self.rebuilt = True
         self.capacity = cap
 
     def candidates(self):
-        raw = self.cands_buf.download(self.nframes * self.capacity, _lib.TRACK_CAND_DTYPE, stream=self.stream)
-        return raw.reshape(self.nframes, self.capacity)
+        return self.side.fetch(self.cands_buf, (self.nframes, self.capacity), _lib.TRACK_CAND_DTYPE)
 
     def run(self):
-        rec = self.alloc("records", 256 * max(self.nframes, 1) * self.plan.ntracks)
-        self.plan.run(self.counts_buf.ptr, self.cands_buf.ptr, self.nframes, rec.ptr, self.stream)
-        out = rec.download(self.nframes * self.plan.ntracks, _lib.TRACK_RECORD_DTYPE, stream=self.stream)
-        return out.reshape(self.nframes, self.plan.ntracks)
+        side, ntracks = self.side, self.plan.ntracks
+        with side.device():
+            rec = side.scratch("records", 256 * max(self.nframes, 1) * ntracks)
+            self.plan.run(self.counts_buf.ptr, self.cands_buf.ptr, self.nframes, rec.ptr, side.stream)
+            return side.fetch(rec, (self.nframes, ntracks), _lib.TRACK_RECORD_DTYPE)
 
 
-class _TorchBuf:
-    """a device byte buffer from torch's allocator with DeviceBuffer's download()"""
-
-    def __init__(self, nbytes, device):
-        import torch
-        self.t = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
-        self.ptr = self.t.data_ptr()
-
-    def download(self, shape, dtype, stream=None):
-        out = np.empty(shape, dtype=dtype)
-        check(lib().prc_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes, stream))
-        check(lib().prc_stream_sync(stream))
-        return out
-
-
-def _device_measure(x, frame_extent, ntracks=1, capacity=None, percentile=TRACK_PERCENTILE, start_capacity=None):
+def _device_measure(x, frame_extent, ntracks=1, capacity=None, percentile=TRACK_PERCENTILE, start_capacity=None, side=None):
     """measure a 2-D frame or [nframes, H, W] stack: numpy (staged) or a torch device tensor (on its stream)"""
-    if _lib.is_device_tensor(x):
-        import torch
-        t = x.to(torch.float32).contiguous()
-        nframes, H, W = _frames_shape(t)
-        stream = _lib.torch_stream_ptr(t.device)
-        with torch.cuda.device(t.device):
-            m = _Measured(t.data_ptr(), nframes, H, W, frame_extent, ntracks, lambda name, nb: _TorchBuf(nb, t.device),
-                          stream, percentile, capacity, start_capacity)
-        m.keep = t
-        return m
-    f = np.ascontiguousarray(x, dtype=np.float32)
-    nframes, H, W = _frames_shape(f)
-    _lib.require_gpu()
-    dx = _lib.DeviceBuffer(f.nbytes)
-    dx.upload(f)
-    m = _Measured(dx.ptr, nframes, H, W, frame_extent, ntracks, lambda name, nb: _lib.DeviceBuffer(nb), None,
-                  percentile, capacity, start_capacity)
-    m.keep = dx
-    return m
+    side = side or residence.of(x, pooled=False)
+    nframes, H, W = _frames_shape(residence.shape(x))
+    return _Measured(side, side.put("frames", x, np.float32), nframes, H, W, frame_extent, ntracks, percentile, capacity,
+                     start_capacity)
 
 
 def _cands_to_meas(c, count):
     c = c[:count]
     return np.stack((c["range"], c["doppler"], c["strength"]))
+
+
+def _cands_tensors(m):
+    """(counts, meas, index) of a _Measured / _Plots on the torch side, as get_measurements documents them"""
+    import torch
+    N, cap = m.nframes, m.capacity
+    raw = m.cands_buf.t[:32 * N * cap]
+    meas = raw.view(torch.float64).view(N, cap, 4)[:, :, [1, 2, 0]].permute(0, 2, 1).contiguous()
+    index = raw.view(torch.int64).view(N, cap, 4)[:, :, 3].contiguous()
+    return m.counts_buf.t[:4 * N].view(torch.int32).clone(), meas, index
 
 
 def get_measurements(dataFrame, p, frame_extent):
@@ -355,18 +315,12 @@ def get_measurements(dataFrame, p, frame_extent):
     reference's fliplr(frame.T) order first).  ``p`` is ignored, as in the reference (always the 99.8th percentile).
     A torch device stack [N, H, W] returns ``(counts, meas, index)`` on the device instead: int32 [N], float64
     [N, 3, capacity] (range, Doppler, strength; entries past counts[i] unused) and int64 [N, capacity] flat indices."""
-    if _lib.is_device_tensor(dataFrame):
-        import torch
-        m = _device_measure(dataFrame, frame_extent)
-        raw = m.cands_buf.t[:32 * m.nframes * m.capacity].view(torch.float64).view(m.nframes, m.capacity, 4)
-        meas = raw[:, :, [1, 2, 0]].permute(0, 2, 1).contiguous()
-        index = m.cands_buf.t[:32 * m.nframes * m.capacity].view(torch.int64).view(m.nframes, m.capacity, 4)[:, :, 3]
-        counts = m.counts_buf.t[:4 * m.nframes].view(torch.int32).clone()
-        return counts, meas, index.contiguous()
-    x = np.asarray(dataFrame)
-    if x.ndim != 2:
+    side = residence.of(dataFrame, pooled=False)
+    if not side.torch and np.ndim(dataFrame) != 2:
         raise ValueError("get_measurements takes one 2-D frame (a torch device stack for batches)")
-    m = _device_measure(x, frame_extent)
+    m = _device_measure(dataFrame, frame_extent, side=side)
+    if side.torch:
+        return _cands_tensors(m)
     return _cands_to_meas(m.candidates()[0], int(m.counts[0]))
 
 
@@ -392,14 +346,8 @@ def multitarget_tracker(data, frame_extent, N_TRACKS):
     """multitarget_tracker (target_detection.py:455-537): ``data`` is numpy (H, W, Nframes) as the reference takes it
     (converted to float32), or a torch device tensor [N, H, W]; frame_extent = [max Doppler, max range].  Returns the
     reference's (Nframes, N_TRACKS) array of target_track_dtype."""
-    if _lib.is_device_tensor(data):
-        x = data
-    else:
-        d = np.asarray(data)
-        if d.ndim != 3:
-            raise ValueError("multitarget_tracker takes (H, W, Nframes) frames")
-        x = np.moveaxis(d, 2, 0)
-    m = _device_measure(x, frame_extent, int(N_TRACKS))
+    side, x, _ = _maps_stack(data, "multitarget_tracker")
+    m = _device_measure(x, frame_extent, int(N_TRACKS), side=side)
     return _records_to_history(m.run(), int(N_TRACKS))
 
 
@@ -417,21 +365,23 @@ def track_maps(xambg, frame_extent, N_TRACKS=10, fw=18, gw=4, cfar="mean", cfar_
     PrcoreError, as the tracker's overflow does."""
     if measure not in ("percentile", "plots"):
         raise ValueError(f"measure is 'percentile' or 'plots', not {measure!r}")
-    if measure == "plots":
-        if plot_thresh is None:
-            raise ValueError("measure='plots' needs plot_thresh")
-        return _track_plots(xambg, frame_extent, int(N_TRACKS), fw, gw, cfar, cfar_rank, float(plot_thresh),
-                            plot_connectivity, plot_max_cells, plot_capacity)
-    if _lib.is_device_tensor(xambg):
-        cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
-        if cf.dim() == 2:
-            cf = cf.unsqueeze(0)
-        return multitarget_tracker(cf, frame_extent, N_TRACKS)
-    x = np.moveaxis(np.asarray(xambg), 2, 0)
-    _lib.require_gpu()
-    do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank)
-    m = _Measured(do.ptr, nframes, H, W, frame_extent, int(N_TRACKS), lambda name, nb: _lib.DeviceBuffer(nb), None)
-    return _records_to_history(m.run(), int(N_TRACKS))
+    if measure == "plots" and plot_thresh is None:
+        raise ValueError("measure='plots' needs plot_thresh")
+    _check_cfar(cfar)
+    ntracks = int(N_TRACKS)
+    side, x, cplx = _maps_stack(xambg, "track_maps")
+    shape = nframes, H, W = tuple(int(v) for v in x.shape)
+    plots = measure == "plots"
+    if plots:
+        _plots_check_host(H, W, float(plot_thresh), frame_extent, plot_connectivity, 8, 4, plot_max_cells, plot_capacity, nframes)
+    xin = side.put("maps", x, _map_dtype(cplx))
+    # with plots the order-statistic CFAR runs on the plain scale, and the maps themselves are the plots' weights
+    cf = _chain_cfar(side, xin, shape, cplx, fw, gw, cfar, cfar_rank, "plain" if plots else "reference")
+    if not plots:
+        return _records_to_history(_Measured(side, cf, nframes, H, W, frame_extent, ntracks).run(), ntracks)
+    m = _Plots(side, cf, xin, cplx, nframes, H, W, float(plot_thresh), frame_extent, connectivity=plot_connectivity,
+               max_cells=plot_max_cells, capacity=plot_capacity)
+    return _records_to_history(_plots_run_tracker(m, H, W, ntracks, frame_extent), ntracks)
 
 
 # ---- plot extraction (beyond the reference; DESIGN.md section 20) -------------------------------------------------------
@@ -439,46 +389,49 @@ PLOTS_DEFAULT_CAPACITY = 512
 
 
 class _Plots:
-    """counts + one prc_track_cand per plot of a stack of statistic frames on the device (prc_plots).  A bound left at
+    """counts + one prc_track_cand per plot of a resident stack of statistic frames (prc_plots; ``stat`` and ``weight`` are
+    handles, weight may be None).  A bound left at
     None is sized from what the call reports, as _Measured sizes its capacity: after a run ncells / counts are read, and if
     a frame exceeded ``max_cells`` the stack is run again at the exact maximum (the workspace path if that is above
     PRC_PLOTS_LDS_CELLS); if then, or at first, a frame has more plots than ``capacity``, once more at that exact maximum
     (the plot count of a frame over max_cells is only known after the first re-run).  A pinned bound is never changed: the
     caller sees the overflow in ncells / counts.  ``start_max_cells`` / ``start_capacity`` only replace the first guesses."""
 
-    def __init__(self, stat_ptr, weight_ptr, complex_weight, nframes, H, W, thresh, frame_extent, alloc, stream,
-                 connectivity=8, range_guard=8, doppler_guard=4, max_cells=None, capacity=None, want_info=False,
-                 start_max_cells=None, start_capacity=None):
-        self.alloc, self.stream, self.nframes = alloc, stream, nframes
+    def __init__(self, side, stat, weight, complex_weight, nframes, H, W, thresh, frame_extent, connectivity=8, range_guard=8,
+                 doppler_guard=4, max_cells=None, capacity=None, want_info=False, start_max_cells=None, start_capacity=None):
+        self.side, self.stat, self.weight, self.nframes = side, stat, weight, nframes
         mc = int(max_cells or start_max_cells or _lib.PLOTS_LDS_CELLS)
         cap = int(capacity or start_capacity or PLOTS_DEFAULT_CAPACITY)
         nf = max(nframes, 1)
-        self.counts_buf = alloc("plot_counts", 4 * nf)
-        self.ncells_buf = alloc("plot_ncells", 4 * nf)
+        self.info_buf = None
         self.runs = 0
-        while True:
-            desc = engine.plots_desc(H, W, thresh, frame_extent, connectivity, range_guard, doppler_guard, mc, cap,
-                                     complex_weight)
-            nws = engine.plots_workspace_bytes(desc, nframes)
-            self.cands_buf = alloc("plot_cands", 32 * nf * cap)
-            self.info_buf = alloc("plot_info", _lib.PLOT_INFO_DTYPE.itemsize * nf * cap) if want_info else None
-            ws = alloc("plot_ws", nws) if nws else None
-            check(lib().prc_memset(self.cands_buf.ptr, 0, 32 * nf * cap, stream))        # slots past a count read as zeros
-            if want_info:
-                check(lib().prc_memset(self.info_buf.ptr, 0, _lib.PLOT_INFO_DTYPE.itemsize * nf * cap, stream))
-            engine.plots_execute(desc, stat_ptr, weight_ptr, nframes, self.counts_buf.ptr, self.ncells_buf.ptr,
-                                 self.cands_buf.ptr, self.info_buf.ptr if want_info else None, ws.ptr if ws else None, stream)
-            self.runs += 1
-            self.counts = self.counts_buf.download(nframes, np.int32, stream=stream)
-            self.ncells = self.ncells_buf.download(nframes, np.int32, stream=stream)
-            need_mc = int(self.ncells.max()) if nframes else 0
-            need_cap = int(self.counts.max()) if nframes else 0
-            grow_mc = max_cells is None and need_mc > mc
-            grow_cap = capacity is None and need_cap > cap
-            if not (grow_mc or grow_cap) or self.runs == 3:
-                break
-            mc = need_mc if grow_mc else mc
-            cap = need_cap if grow_cap else cap
+        with side.device():
+            self.counts_buf = side.scratch("plot_counts", 4 * nf)
+            self.ncells_buf = side.scratch("plot_ncells", 4 * nf)
+            while True:
+                desc = engine.plots_desc(H, W, thresh, frame_extent, connectivity, range_guard, doppler_guard, mc, cap,
+                                         complex_weight)
+                nws = engine.plots_workspace_bytes(desc, nframes)
+                self.cands_buf = side.scratch("plot_cands", 32 * nf * cap)
+                if want_info:
+                    self.info_buf = side.scratch("plot_info", _lib.PLOT_INFO_DTYPE.itemsize * nf * cap)
+                ws = side.scratch("plot_ws", nws)
+                side.zero(self.cands_buf, 32 * nf * cap)                                     # slots past a count read as zeros
+                if want_info:
+                    side.zero(self.info_buf, _lib.PLOT_INFO_DTYPE.itemsize * nf * cap)
+                engine.plots_execute(desc, stat, weight, nframes, self.counts_buf, self.ncells_buf, self.cands_buf, self.info_buf,
+                                     ws, side.stream)
+                self.runs += 1
+                self.counts = side.fetch(self.counts_buf, nframes, np.int32)
+                self.ncells = side.fetch(self.ncells_buf, nframes, np.int32)
+                need_mc = int(self.ncells.max()) if nframes else 0
+                need_cap = int(self.counts.max()) if nframes else 0
+                grow_mc = max_cells is None and need_mc > mc
+                grow_cap = capacity is None and need_cap > cap
+                if not (grow_mc or grow_cap) or self.runs == 3:
+                    break
+                mc = need_mc if grow_mc else mc
+                cap = need_cap if grow_cap else cap
         self.max_cells, self.capacity = mc, cap
 
     def stored(self):
@@ -489,12 +442,10 @@ class _Plots:
         return bool((self.ncells > self.max_cells).any() or (self.counts > self.capacity).any())
 
     def candidates(self):
-        raw = self.cands_buf.download(self.nframes * self.capacity, _lib.TRACK_CAND_DTYPE, stream=self.stream)
-        return raw.reshape(self.nframes, self.capacity)
+        return self.side.fetch(self.cands_buf, (self.nframes, self.capacity), _lib.TRACK_CAND_DTYPE)
 
     def info(self):
-        raw = self.info_buf.download(self.nframes * self.capacity, _lib.PLOT_INFO_DTYPE, stream=self.stream)
-        return raw.reshape(self.nframes, self.capacity)
+        return self.side.fetch(self.info_buf, (self.nframes, self.capacity), _lib.PLOT_INFO_DTYPE)
 
 
 def _plots_check_host(H, W, thresh, frame_extent, connectivity, range_guard, doppler_guard, max_cells, capacity, nframes):
@@ -509,46 +460,20 @@ def _plots_check_host(H, W, thresh, frame_extent, connectivity, range_guard, dop
 
 def _device_plots(stat, thresh, frame_extent, weight, **kw):
     """_Plots of a 2-D frame or [nframes, H, W] stack: numpy (staged, null stream) or a torch device tensor (its stream)"""
-    dev = _lib.is_device_tensor(stat)
-    if weight is not None and _lib.is_device_tensor(weight) != dev:
-        raise ValueError("stat and weight are both NumPy arrays or both device tensors")
-    if dev:
-        import torch
-        t = stat.to(torch.float32).contiguous()
-        w = None if weight is None else weight.to(torch.complex64 if weight.is_complex() else torch.float32).contiguous()
-        shape, wshape, cplx = tuple(t.shape), None if w is None else tuple(w.shape), w is not None and w.is_complex()
-    else:
-        t = np.ascontiguousarray(stat, dtype=np.float32)
-        w = None
-        if weight is not None:
-            w = np.asarray(weight)
-            w = np.ascontiguousarray(w, dtype=np.complex64 if np.iscomplexobj(w) else np.float32)
-        shape, wshape, cplx = t.shape, None if w is None else w.shape, w is not None and np.iscomplexobj(w)
+    side = residence.of(stat, weight, pooled=False, mixed="stat and weight are both NumPy arrays or both device tensors")
+    shape = residence.shape(stat)
+    wshape = None if weight is None else residence.shape(weight)
+    cplx = weight is not None and residence.iscomplex(weight)
     if len(shape) not in (2, 3):
         raise ValueError("extract_plots takes a frame [H, W] or a stack [nframes, H, W]")
     if wshape is not None and wshape != shape:
         raise ValueError(f"weight has shape {wshape}, stat {shape}")
-    nframes, H, W = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    nframes, H, W = _frames_shape(shape)
     _plots_check_host(H, W, thresh, frame_extent, kw.get("connectivity", 8), kw.get("range_guard", 8),
                       kw.get("doppler_guard", 4), kw.get("max_cells"), kw.get("capacity"), nframes)
-    if dev:
-        stream = _lib.torch_stream_ptr(t.device)
-        with torch.cuda.device(t.device):
-            m = _Plots(t.data_ptr(), None if w is None else w.data_ptr(), cplx, nframes, H, W, thresh, frame_extent,
-                       lambda name, nb: _TorchBuf(nb, t.device), stream, **kw)
-        m.keep = (t, w)
-        return m
-    _lib.require_gpu()
-    dx = _lib.DeviceBuffer(t.nbytes)
-    dx.upload(t)
-    dw = None
-    if w is not None:
-        dw = _lib.DeviceBuffer(w.nbytes)
-        dw.upload(w)
-    m = _Plots(dx.ptr, None if dw is None else dw.ptr, cplx, nframes, H, W, thresh, frame_extent,
-               lambda name, nb: _lib.DeviceBuffer(nb), None, **kw)
-    m.keep = (dx, dw)
-    return m
+    t = side.put("stat", stat, np.float32)
+    w = None if weight is None else side.put("weight", weight, _map_dtype(cplx))
+    return _Plots(side, t, w, cplx, nframes, H, W, thresh, frame_extent, **kw)
 
 
 def extract_plots(stat, thresh, frame_extent, *, weight=None, connectivity=8, range_guard=8, doppler_guard=4,
@@ -573,16 +498,13 @@ def extract_plots(stat, thresh, frame_extent, *, weight=None, connectivity=8, ra
                       doppler_guard=doppler_guard, max_cells=max_cells, capacity=capacity, want_info=return_info,
                       start_max_cells=start_max_cells, start_capacity=start_capacity)
     N, cap = m.nframes, m.capacity
-    if _lib.is_device_tensor(stat):
+    if m.side.torch:
         import torch
-        raw = m.cands_buf.t[:32 * N * cap]
-        meas = raw.view(torch.float64).view(N, cap, 4)[:, :, [1, 2, 0]].permute(0, 2, 1).contiguous()
-        index = raw.view(torch.int64).view(N, cap, 4)[:, :, 3].contiguous()
-        counts = m.counts_buf.t[:4 * N].view(torch.int32).clone()
+        out = _cands_tensors(m)
         if not return_info:
-            return counts, meas, index
+            return out
         nb = _lib.PLOT_INFO_DTYPE.itemsize
-        return counts, meas, index, m.info_buf.t[:nb * N * cap].view(N, cap, nb).clone(), m.ncells_buf.t[:4 * N].view(torch.int32).clone()
+        return out + (m.info_buf.t[:nb * N * cap].view(N, cap, nb).clone(), m.ncells_buf.t[:4 * N].view(torch.int32).clone())
     c = m.candidates()
     if len(np.shape(stat)) == 2:
         k = int(m.stored()[0])
@@ -593,53 +515,18 @@ def extract_plots(stat, thresh, frame_extent, *, weight=None, connectivity=8, ra
     return out + (m.info(), m.ncells) if return_info else out
 
 
-def _track_plots(xambg, frame_extent, ntracks, fw, gw, cfar, cfar_rank, thresh, connectivity, max_cells, capacity):
-    """CFAR -> prc_plots -> prc_track_run on one stream; the maps themselves are the weights"""
-    if cfar not in ("mean", "os"):
-        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
-    dev = _lib.is_device_tensor(xambg)
-    if dev:
-        import torch
-        x = xambg.to(torch.complex64 if xambg.is_complex() else torch.float32).contiguous()
-        if x.dim() == 2:
-            x = x.unsqueeze(0)
-        shape, cplx = tuple(x.shape), x.is_complex()
-    else:
-        x = np.asarray(xambg)
-        if x.ndim != 3:
-            raise ValueError("track_maps takes (H, W, Nframes) frames")
-        x = np.moveaxis(x, 2, 0)
-        shape, cplx = x.shape, np.iscomplexobj(x)
-    if len(shape) != 3:
-        raise ValueError("track_maps takes a device stack [N, H, W]")
-    nframes, H, W = (int(v) for v in shape)
-    _plots_check_host(H, W, thresh, frame_extent, connectivity, 8, 4, max_cells, capacity, nframes)
-    kw = dict(connectivity=connectivity, max_cells=max_cells, capacity=capacity)
-    if dev:
-        cf = _chain_cfar(x, fw, gw, cfar, cfar_rank, "plain")
-        stream = _lib.torch_stream_ptr(x.device)
-        alloc = lambda name, nb: _TorchBuf(nb, x.device)      # noqa: E731
-        with torch.cuda.device(x.device):
-            m = _Plots(cf.data_ptr(), x.data_ptr(), cplx, nframes, H, W, thresh, frame_extent, alloc, stream, **kw)
-            rec = _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, stream)
-    else:
-        _lib.require_gpu()
-        do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank, "plain")
-        alloc = lambda name, nb: _lib.DeviceBuffer(nb)        # noqa: E731
-        m = _Plots(do.ptr, keep[0].ptr, cplx, nframes, H, W, thresh, frame_extent, alloc, None, **kw)
-        rec = _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, None)
-    return _records_to_history(rec, ntracks)
-
-
-def _plots_run_tracker(m, H, W, ntracks, frame_extent, alloc, stream):
+def _plots_run_tracker(m, H, W, ntracks, frame_extent):
+    """prc_track_run on the plots of ``m``, on its side"""
     if (m.ncells > m.max_cells).any():
         raise _lib.PrcoreError(_lib.PRC_EINVAL, "track_maps: a frame's detections exceeded plot_max_cells")
-    plan = TrackPlan(H, W, ntracks, m.capacity, frame_extent)
-    rec = alloc("records", 256 * max(m.nframes, 1) * ntracks)
-    plan.run(m.counts_buf.ptr, m.cands_buf.ptr, m.nframes, rec.ptr, stream)
-    out = rec.download(m.nframes * ntracks, _lib.TRACK_RECORD_DTYPE, stream=stream)
+    side = m.side
+    with side.device():
+        plan = TrackPlan(H, W, ntracks, m.capacity, frame_extent)
+        rec = side.scratch("records", 256 * max(m.nframes, 1) * ntracks)
+        plan.run(m.counts_buf.ptr, m.cands_buf.ptr, m.nframes, rec.ptr, side.stream)
+        out = side.fetch(rec, (m.nframes, ntracks), _lib.TRACK_RECORD_DTYPE)
     plan.close()
-    return out.reshape(m.nframes, ntracks)
+    return out
 
 
 # ---- track-before-detect (beyond the reference; DESIGN.md section 21) ---------------------------------------------------
@@ -693,49 +580,26 @@ def track_before_detect(stat, frame_extent=None, *, alpha=0.9, doppler_reach=1, 
     ``stat`` is a frame [H, W] or a stack [N, H, W] (H Doppler rows, W range columns), NumPy or a torch device tensor;
     returns ``(score, back)`` of stat's shape, float32 and uint8 (back None with ``return_back=False``): arrays for NumPy,
     tensors on the caller's device and torch's current stream for torch."""
-    dev = _lib.is_device_tensor(stat)
-    if dev:
-        import torch
-        t = stat.to(torch.float32).contiguous()
-        shape = tuple(t.shape)
-    else:
-        t = np.ascontiguousarray(stat, dtype=np.float32)
-        shape = t.shape
+    shape = residence.shape(stat)
     if len(shape) not in (2, 3):
         raise ValueError("track_before_detect takes a frame [H, W] or a stack [nframes, H, W]")
-    nframes, H, W = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    nframes, H, W = _frames_shape(shape)
     desc = engine.tbd_desc(H, W, alpha, doppler_reach, range_reach, clip, range_guard, doppler_guard)
     _tbd_check_host(desc)
     s = _tbd_shifts_host(row_shifts, H)
     if prev is not None and tuple(prev.shape) != (H, W):
         raise ValueError(f"prev has shape {tuple(prev.shape)}, a frame {(H, W)}")
-    if dev:
-        if prev is not None and not _lib.is_device_tensor(prev):
-            raise ValueError("stat and prev are both NumPy arrays or both device tensors")
-        ds = None if s is None else torch.from_numpy(s).to(t.device)
-        dp = None if prev is None else prev.to(torch.float32).contiguous()
-        score = torch.empty_like(t)
-        back = torch.empty(shape, dtype=torch.uint8, device=t.device) if return_back else None
-        if nframes:
-            with torch.cuda.device(t.device):
-                engine.tbd_execute(desc, t, ds, dp, nframes, score, back, _lib.torch_stream_ptr(t.device))
-        return score, back
-    _lib.require_gpu()
-    n = nframes * H * W
-    if n == 0:
-        return np.zeros(shape, np.float32), (np.zeros(shape, np.uint8) if return_back else None)
-    dx, dscore = _lib.DeviceBuffer(4 * n), _lib.DeviceBuffer(4 * n)
-    dx.upload(t)
-    dback = _lib.DeviceBuffer(n) if return_back else None
-    ds = dp = None
-    if s is not None:
-        ds = _lib.DeviceBuffer(4 * H)
-        ds.upload(s)
-    if prev is not None:
-        dp = _lib.DeviceBuffer(4 * H * W)
-        dp.upload(np.ascontiguousarray(prev, dtype=np.float32))
-    engine.tbd_execute(desc, dx, ds, dp, nframes, dscore, dback)
-    return dscore.download(shape, np.float32), (dback.download(shape, np.uint8) if return_back else None)
+    side = residence.of(stat, prev, pooled=False, mixed="stat and prev are both NumPy arrays or both device tensors")
+    if nframes == 0:
+        return side.nothing(shape, np.float32), (side.nothing(shape, np.uint8) if return_back else None)
+    x = side.put("stat", stat, np.float32)
+    ds = None if s is None else side.put("shifts", s, np.int32)
+    dp = None if prev is None else side.put("prev", prev, np.float32)
+    score = side.empty("score", shape, np.float32)
+    back = side.empty("back", shape, np.uint8) if return_back else None
+    with side.device():
+        engine.tbd_execute(desc, x, ds, dp, nframes, score, back, side.stream)
+    return side.result(score, shape, np.float32), (side.result(back, shape, np.uint8) if return_back else None)
 
 
 def tbd_paths(back, ends, depth, row_shifts=None, *, doppler_reach=1, range_reach=1):
@@ -744,7 +608,6 @@ def tbd_paths(back, ends, depth, row_shifts=None, *, doppler_reach=1, range_reac
     where the path stops (no predecessor was chosen, the stack begins) and in the whole row of an end outside the stack.
     ``row_shifts`` and the reaches are those of the track_before_detect call.  NumPy in, NumPy out; torch device tensors in,
     a tensor on the same device and torch's current stream out."""
-    dev = _lib.is_device_tensor(back)
     if len(back.shape) != 3:
         raise ValueError("back is a stack [nframes, H, W]")
     nframes, H, W = (int(v) for v in back.shape)
@@ -754,34 +617,20 @@ def tbd_paths(back, ends, depth, row_shifts=None, *, doppler_reach=1, range_reac
     desc = engine.tbd_desc(H, W, 1.0, doppler_reach, range_reach)
     _tbd_check_host(desc)
     s = _tbd_shifts_host(row_shifts, H)
-    if dev:
-        import torch
-        b = back.to(torch.uint8).contiguous()
-        e = torch.as_tensor(ends, device=b.device).to(torch.int32).contiguous()
-        if e.dim() != 2 or e.shape[1] != 2:
-            raise ValueError("ends is [nends, 2]: frame, cell")
-        paths = torch.empty((e.shape[0], depth), dtype=torch.int32, device=b.device)
-        ds = None if s is None else torch.from_numpy(s).to(b.device)
-        if e.shape[0]:
-            with torch.cuda.device(b.device):
-                engine.tbd_trace(desc, b, ds, nframes, e, e.shape[0], depth, paths, _lib.torch_stream_ptr(b.device))
-        return paths
-    b = np.ascontiguousarray(back, dtype=np.uint8)
-    e = np.ascontiguousarray(ends, dtype=np.int32)
-    if e.ndim != 2 or e.shape[1] != 2:
+    eshape = residence.shape(ends)
+    if len(eshape) != 2 or eshape[1] != 2:
         raise ValueError("ends is [nends, 2]: frame, cell")
-    if e.shape[0] == 0:
-        return np.zeros((0, depth), np.int32)
-    _lib.require_gpu()
-    db, de, dpaths = _lib.DeviceBuffer(b.nbytes), _lib.DeviceBuffer(e.nbytes), _lib.DeviceBuffer(4 * e.shape[0] * depth)
-    db.upload(b)
-    de.upload(e)
-    ds = None
-    if s is not None:
-        ds = _lib.DeviceBuffer(4 * H)
-        ds.upload(s)
-    engine.tbd_trace(desc, db, ds, nframes, de, e.shape[0], depth, dpaths)
-    return dpaths.download((e.shape[0], depth), np.int32)
+    nends = int(eshape[0])
+    side = residence.of(back, pooled=False)
+    if nends == 0:
+        return side.nothing((0, depth), np.int32)
+    b = side.put("back", back, np.uint8)
+    e = side.put("ends", ends if hasattr(ends, "shape") else np.asarray(ends), np.int32)
+    ds = None if s is None else side.put("shifts", s, np.int32)
+    paths = side.empty("paths", (nends, depth), np.int32)
+    with side.device():
+        engine.tbd_trace(desc, b, ds, nframes, e, nends, depth, paths, side.stream)
+    return side.result(paths, (nends, depth), np.int32)
 
 
 def tbd_maps(xambg, frame_extent, frame_interval, wavelength, *, thresh, depth=16, fw=18, gw=4, cfar="os", cfar_rank=None,
@@ -795,20 +644,8 @@ def tbd_maps(xambg, frame_extent, frame_interval, wavelength, *, thresh, depth=1
     as weight and the same guards; every plot's peak cell is the end of one path of ``depth`` cells.
     Returns ``(counts, meas, index, paths)``: the first three as extract_plots returns them for a stack, ``paths`` int32
     [N, capacity, depth] (tbd_paths' rows; -1 in the slots past counts[i])."""
-    if cfar not in ("mean", "os"):
-        raise ValueError(f"cfar is 'mean' or 'os', not {cfar!r}")
-    dev = _lib.is_device_tensor(xambg)
-    if dev:
-        import torch
-        x = xambg if xambg.dim() == 3 else xambg.unsqueeze(0)
-        x = x.to(torch.complex64 if x.is_complex() else torch.float32).contiguous()
-    else:
-        x = np.asarray(xambg)
-        if x.ndim != 3:
-            raise ValueError("tbd_maps takes (H, W, Nframes) frames")
-        x = np.moveaxis(x, 2, 0)
-    if len(x.shape) != 3:
-        raise ValueError("tbd_maps takes a device stack [N, H, W]")
+    _check_cfar(cfar)
+    side, x, cplx = _maps_stack(xambg, "tbd_maps")
     N, H, W = (int(v) for v in x.shape)
     kw = dict(tbd_kw)
     bad = set(kw) - {"alpha", "doppler_reach", "range_reach", "row_shifts", "clip", "range_guard", "doppler_guard", "prev"}
@@ -821,17 +658,17 @@ def tbd_maps(xambg, frame_extent, frame_interval, wavelength, *, thresh, depth=1
                                     kw.get("clip"), **guards))
     _plots_check_host(H, W, float(thresh), frame_extent, plot_connectivity, guards["range_guard"], guards["doppler_guard"],
                       None, None, N)
+    # the stages are the front doors themselves: each returns what the next takes, on the side the maps came from
     if cfar == "os":
         cf = CFAR_2D_OS(x, fw, gw, rank=cfar_rank, scale="plain")
-    elif dev:
-        cf = _chain_cfar(x, fw, gw, cfar, cfar_rank)
     else:
-        cf = CFAR_2D_abs(x, fw, gw) if np.iscomplexobj(x) else CFAR_2D(x, fw, gw)
+        cf = CFAR_2D_abs(x, fw, gw) if cplx else CFAR_2D(x, fw, gw)
     score, back = track_before_detect(cf, frame_extent, **kw)
     counts, meas, index, info, _ = extract_plots(score, thresh, frame_extent, connectivity=plot_connectivity, return_info=True,
                                                  **guards)
     cap = int(index.shape[1])
-    if dev:
+    if side.torch:
+        import torch
         peak = info[:, :, 44:48].contiguous().view(torch.int32).view(N, cap)          # prc_plot_info.peak
         valid = torch.arange(cap, device=x.device)[None, :] < counts[:, None]
         frame = torch.arange(N, device=x.device, dtype=torch.int32)[:, None].expand(N, cap)
@@ -894,21 +731,19 @@ def _strack_desc(H, W, dtype, range_extent, doppler_extent):
     return d
 
 
-def _strack_run(frames_ptr, nframes, H, W, dtype, range_extent, doppler_extent, state, alloc, stream):
-    """prc_strack_run on device frames [nframes][H][W]; returns the records as STRACK_RECORD_DTYPE"""
+def _strack_run(side, frames, nframes, H, W, dtype, range_extent, doppler_extent, state=None):
+    """prc_strack_run on the resident frames [nframes][H][W] (``frames``: their handle; ``state``: a prc_strack_record to
+    resume from); returns the history"""
     d = _strack_desc(H, W, dtype, range_extent, doppler_extent)
     nb = C.c_size_t(0)
     check(lib().prc_strack_workspace_bytes(C.byref(d), int(nframes), C.byref(nb)))
-    ws = alloc(nb.value)
-    rec = alloc(_lib.STRACK_RECORD_DTYPE.itemsize * max(nframes, 1))
-    st_ptr = None
-    if state is not None:
-        st = _lib.DeviceBuffer(_lib.STRACK_RECORD_DTYPE.itemsize)
-        st.upload(_strack_state_record(state))
-        st_ptr = st.ptr
-    check(lib().prc_strack_run(C.byref(d), frames_ptr, int(nframes), st_ptr, rec.ptr, ws.ptr, stream))
-    out = rec.download(nframes, _lib.STRACK_RECORD_DTYPE, stream=stream)
-    return out
+    with side.device():
+        ws = side.scratch("strack_ws", nb.value)                               # no bytes only for no frames
+        rec = side.scratch("strack_rec", _lib.STRACK_RECORD_DTYPE.itemsize * max(nframes, 1))
+        st = None if state is None else side.put("strack_state", state.view(np.uint8), np.uint8)
+        check(lib().prc_strack_run(C.byref(d), frames.ptr, int(nframes), engine._ptr(st), rec.ptr, engine._ptr(ws), side.stream))
+        out = side.fetch(rec, nframes, _lib.STRACK_RECORD_DTYPE)
+    return _strack_records_to_history(out, range_extent, doppler_extent)
 
 
 def simple_target_tracker(data, rangeExtent, dopplerExtent, *, state=None):
@@ -918,29 +753,12 @@ def simple_target_tracker(data, rangeExtent, dopplerExtent, *, state=None):
     reference does on the frames as float64 (a float64 frame may differ only where the reference's own division by the
     frame mean merges two values within about one ulp).  ``state=`` (the one extension) is a history row -- the last
     one of an earlier call -- to resume from; without it the track starts from the reference's initial state."""
-    if _lib.is_device_tensor(data):
-        import torch
-        t = data if data.dtype in (torch.float32, torch.float64) else data.to(torch.float64)
-        t = t.contiguous()
-        if t.dim() != 3:
-            raise ValueError("simple_target_tracker takes a device stack [N, H, W]")
-        N, H, W = t.shape
-        dt = _lib.REAL_F32 if t.dtype == torch.float32 else _lib.REAL_F64
-        with torch.cuda.device(t.device):
-            rec = _strack_run(t.data_ptr(), N, H, W, dt, rangeExtent, dopplerExtent, state,
-                              lambda nb: _TorchBuf(nb, t.device), _lib.torch_stream_ptr(t.device))
-        return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
-    d = np.asarray(data)
-    if d.ndim != 3:
-        raise ValueError("simple_target_tracker takes (H, W, Nframes) frames")
-    f = np.ascontiguousarray(np.moveaxis(d, 2, 0), dtype=np.float32 if d.dtype == np.float32 else np.float64)
-    N, H, W = f.shape
-    _lib.require_gpu()
-    dx = _lib.DeviceBuffer(f.nbytes)
-    dx.upload(f)
-    rec = _strack_run(dx.ptr, N, H, W, _lib.REAL_F32 if f.dtype == np.float32 else _lib.REAL_F64, rangeExtent,
-                      dopplerExtent, state, lambda nb: _lib.DeviceBuffer(nb), None)
-    return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
+    side, x, _ = _maps_stack(data, "simple_target_tracker", frame_ok=False)
+    N, H, W = (int(v) for v in x.shape)
+    f32 = residence.dtype_name(x) == "float32"
+    state = None if state is None else _strack_state_record(state)
+    frames = side.put("frames", x, np.float32 if f32 else np.float64)
+    return _strack_run(side, frames, N, H, W, _lib.REAL_F32 if f32 else _lib.REAL_F64, rangeExtent, dopplerExtent, state)
 
 
 def simple_track_maps(xambg, rangeExtent, dopplerExtent, fw=18, gw=4, cfar="mean", cfar_rank=None):
@@ -948,17 +766,11 @@ def simple_track_maps(xambg, rangeExtent, dopplerExtent, fw=18, gw=4, cfar="mean
     (CFAR_2D_abs; CFAR_2D for a real magnitude stack) -> simple_target_tracker on the float32 CFAR maps.  ``xambg`` is
     a torch device tensor [N, H, W] or numpy (H, W, Nframes) as the script loads it.  ``cfar="os"`` puts CFAR_2D_OS
     (reference scale, rank ``cfar_rank``) in the cell average's place."""
-    if _lib.is_device_tensor(xambg):
-        cf = _chain_cfar(xambg, fw, gw, cfar, cfar_rank)
-        if cf.dim() == 2:
-            cf = cf.unsqueeze(0)
-        return simple_target_tracker(cf, rangeExtent, dopplerExtent)
-    x = np.moveaxis(np.asarray(xambg), 2, 0)
-    _lib.require_gpu()
-    do, nframes, H, W, keep = _chain_cfar_staged(x, fw, gw, cfar, cfar_rank)
-    rec = _strack_run(do.ptr, nframes, H, W, _lib.REAL_F32, rangeExtent, dopplerExtent, None,
-                      lambda nb: _lib.DeviceBuffer(nb), None)
-    return _strack_records_to_history(rec, rangeExtent, dopplerExtent)
+    _check_cfar(cfar)
+    side, x, cplx = _maps_stack(xambg, "simple_track_maps")
+    shape = N, H, W = tuple(int(v) for v in x.shape)
+    cf = _chain_cfar(side, side.put("maps", x, _map_dtype(cplx)), shape, cplx, fw, gw, cfar, cfar_rank)
+    return _strack_run(side, cf, N, H, W, _lib.REAL_F32, rangeExtent, dopplerExtent)
 
 
 # ---- sub-cell peak refinement of exact ambiguity patches (range_doppler_processing.xambg_patch) ------------------------
@@ -978,26 +790,20 @@ def refine_peaks(X, lags, dopplers, doppler_step):
     if rec.shape[0] != npatches:
         raise ValueError(f"{npatches} patches but {rec.shape[0]} origins")
     desc = engine.patch_desc(1, nlags, ndoppler, 1.0, doppler_step)
-    if _lib.is_device_tensor(X):
-        import torch
-        with torch.cuda.device(X.device):
-            x = X.to(torch.complex64).contiguous()
-            raw = torch.empty((npatches, _lib.PATCH_PEAK_DTYPE.itemsize), dtype=torch.uint8, device=x.device)
-            d_rec = torch.from_numpy(rec.view(np.uint8)).to(x.device)
-            if npatches:
-                engine.xambg_patch_peaks(desc, d_rec, npatches, x, raw, _lib.torch_stream_ptr(x.device))
-        f64, f32, i32 = raw.view(torch.float64), raw.view(torch.float32), raw.view(torch.int32)
-        return {"lag": f64[:, 0], "doppler": f64[:, 1], "amplitude": f32[:, 4], "d": i32[:, 5], "l": i32[:, 6],
-                "flags": i32[:, 7]}
-    x = np.ascontiguousarray(X, dtype=np.complex64)
+    side = residence.of(X)
+    nb = _lib.PATCH_PEAK_DTYPE.itemsize
     if npatches == 0:
-        return np.zeros(0, dtype=_lib.PATCH_PEAK_DTYPE)
-    _lib.require_gpu()
-    st = engine.staging()
-    d_x = st.get("xp_out", x.nbytes)
-    d_rec = st.get("xp_rec", rec.nbytes)
-    d_pk = st.get("xp_peaks", npatches * _lib.PATCH_PEAK_DTYPE.itemsize)
-    d_x.upload(x)
-    d_rec.upload(rec.view(np.uint8))
-    engine.xambg_patch_peaks(desc, d_rec, npatches, d_x, d_pk)
-    return d_pk.download((npatches,), _lib.PATCH_PEAK_DTYPE)
+        raw = side.nothing((0, nb), np.uint8)
+    else:
+        x = side.put("xp_out", X, np.complex64)
+        d_rec = side.put("xp_rec", rec.view(np.uint8), np.uint8)
+        peaks = side.empty("xp_peaks", (npatches, nb), np.uint8)
+        with side.device():
+            engine.xambg_patch_peaks(desc, d_rec, npatches, x, peaks, side.stream)
+        raw = side.result(peaks, (npatches, nb), np.uint8)
+    if not side.torch:
+        return raw.view(_lib.PATCH_PEAK_DTYPE).reshape(npatches)
+    import torch
+    f64, f32, i32 = raw.view(torch.float64), raw.view(torch.float32), raw.view(torch.int32)
+    return {"lag": f64[:, 0], "doppler": f64[:, 1], "amplitude": f32[:, 4], "d": i32[:, 5], "l": i32[:, 6],
+            "flags": i32[:, 7]}

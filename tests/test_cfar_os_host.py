@@ -110,9 +110,10 @@ def test_argument_errors_need_no_device():
 
 def test_chain_keyword_is_checked():
     from passiveradar_amd.plotting_tools import render_maps
-    from passiveradar_amd.target_detection import _chain_cfar_staged
+    from passiveradar_amd import residence
+    from passiveradar_amd.target_detection import _chain_cfar
     with pytest.raises(ValueError, match="cfar"):
-        _chain_cfar_staged(np.ones((2, 8, 9), np.float32), 18, 4, "median", None)
+        _chain_cfar(residence.HostSide(pooled=False), None, (2, 8, 9), False, 18, 4, "median", None)
     with pytest.raises(ValueError, match="cfar"):
         render_maps(np.ones((4, 3, 2)), cfar="median")
 
