@@ -36,7 +36,7 @@
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
  *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots, tests/test_gpu_tbd_bounds.py prc_tbd and
- *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel).
+ *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel, tests/test_gpu_channelize_bounds.py prc_channelize).
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -53,7 +53,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, sixth edition (additions only, the number stays as for the editions below): prc_echo_desc, prc_echo_atom, prc_echo_fit,
+#define PRC_VERSION 680   /* 680, seventh edition (additions only, the number stays as for the editions below): prc_channelize_desc, prc_channelize,
+                             PRC_OPT_CHANNELIZE_FORM (uniform polyphase filter bank: K of M channels out of one pass over the raw samples);
+                             680, sixth edition (additions only, the number stays as for the editions below): prc_echo_desc, prc_echo_atom, prc_echo_fit,
                              prc_echo_cancel_workspace_bytes, prc_echo_cancel (joint least-squares removal of strong echoes at any lag and Doppler);
                              680, fifth edition (additions only, the number stays as for the editions below): prc_tbd_desc, prc_tbd, prc_tbd_trace,
                              PRC_OPT_TBD_FRAMES, PRC_OPT_TBD_ROWS (track-before-detect: Viterbi integration of a stack of CFAR maps, on device);
@@ -157,7 +159,9 @@ typedef enum prc_option {
                                      where LDS does not hold them; one frame per launch where it holds none).  Same bytes out at every value */
     PRC_OPT_TBD_ROWS = 16,        /* prc_tbd, read per call: rows of the band a workgroup of the time-blocked form owns.  0 (default) =
                                      from the shape (see prc_tbd); 1 .. 4096 = forced (lowered to what LDS holds).  Same bytes out       */
-    PRC_OPT_COUNT_ = 17
+    PRC_OPT_CHANNELIZE_FORM = 17, /* prc_channelize, read per call: 0 (default) = the LDS-tile form where the tile fits
+                                     PRC_CHANNELIZE_TILE_MAX_BYTES, the direct form elsewhere; 1 = the direct form always (tests) */
+    PRC_OPT_COUNT_ = 18
 } prc_option;
 int prc_set_option(int32_t option, int64_t value);     /* PRC_EINVAL for an unknown option or a value out of range */
 int prc_get_option(int32_t option, int64_t* value);
@@ -901,6 +905,50 @@ int prc_shift(const void* x, void* y, int64_t rows, int64_t row_bytes, int64_t s
  * synchronises.  y may be x.  PRC_EINVAL: null pointers, n < 1, is_complex not 0 / 1. */
 int prc_normalize_workspace_bytes(int64_t n, size_t* bytes);
 int prc_normalize(const void* x, void* y, int64_t n, int32_t is_complex, void* workspace, void* stream);
+
+/* channelize (signal_utils.channelize, beside channel_preprocessing in this section): a uniform polyphase filter bank, K of M
+ * channels out of one pass over the raw samples.  Channel k of nchan = M is centred at k fs / M.  With real taps h of odd length L = ntaps, c = (L - 1) / 2, x zero outside
+ * [0, n) and `start` the stream index of x[0], row i of the result is channel k_i = channels[i]:
+ *   y[i][j] = sum_{t < L} h[t] x[j dec + c - t] w^((k_i (start + j dec + c - t)) mod M),  w = exp(-2 pi i / M),  j < ceil(n / dec)
+ * -- what prc_fir_decimate with mix gives for fc = -k_i fs / M if its phase ramp were exact.  dec need not equal, divide or
+ * be divided by M.  The exponent is an integer reduced modulo M (start is an int64: 2^40 is as accurate as 0), the rotation
+ * is read from `twiddles`, DEVICE float2[M] = (cos, sin)(2 pi r / M) evaluated in float64 and rounded to float32.  The FIR is
+ * computed once per output time and shared by the channels: grouped by tap phase p = t mod M it leaves M partial sums u_p,
+ * and channel k is w^(k (start + j dec + c)) sum_p w^(-k p) u_p -- an M-point DFT at the output rate.
+ * taps: DEVICE float32[ntaps]; channels: DEVICE int32[nsel], each in [-M/2, M) (k and k - M are the same channel; any other
+ * value is folded modulo M), duplicates allowed; x: DEVICE raw_dtype (interleaved I,Q scalars of deinterleave_IQ, or
+ * complex64); out: DEVICE complex64, row i at element i * out_stride.
+ * Memory: x is read only inside [0, n) samples, taps inside [0, ntaps), twiddles inside [0, M), channels inside [0, nsel);
+ * exactly the nsel * ceil(n / dec) promised elements of out are written and nothing else is.  x needs the alignment of its
+ * scalar type, out and twiddles 8 bytes, taps and channels 4.
+ * Two forms, chosen from dec and ntaps alone: where the (256 + ceil(c / dec) + floor(c / dec) + 1 | 1) * dec * 8 bytes of a
+ * tile are at most PRC_CHANNELIZE_TILE_MAX_BYTES (dec <= 73 with decimate's 20 dec + 1 taps) a wavefront stages the raw
+ * samples of 256 output times in LDS, sample-phase-major modulo dec, and runs the sums above with wave-uniform taps and
+ * twiddles, eight channels at a time over the same staged tile; anything else runs one wavefront per output time and
+ * channel, lanes striding over the taps (PRC_OPT_CHANNELIZE_FORM = 1 forces this form).  Sums are float32 fused
+ * multiply-adds in a fixed order, no atomics: two calls give the same bits, and the bits of a channel do not depend on which
+ * other channels were asked for or in what order.  One kernel on `stream`; neither allocates nor synchronises (it can be
+ * captured).  n == 0 is a no-op.
+ * PRC_EINVAL: a bad descriptor header, nchan outside 2 .. PRC_CHANNELIZE_MAX_CHAN, dec < 1, ntaps < 1 or even, a bad
+ * raw_dtype, nsel outside 1 .. PRC_CHANNELIZE_MAX_SEL, n < 0, out_stride < ceil(n / dec) with nsel > 1, null or misaligned
+ * pointers; PRC_ESHAPE: ntaps >= 2^24. */
+typedef struct prc_channelize_desc {
+    uint32_t struct_size;  /* sizeof(prc_channelize_desc) as the host compiled it (see Conventions)       */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                          */
+    int32_t nchan;         /* M: channels of the bank, centred at k fs / M; 2 .. PRC_CHANNELIZE_MAX_CHAN */
+    int32_t dec;           /* D >= 1: keep every D-th output time                                     */
+    int32_t ntaps;         /* odd; decimate's own filter is 20 D + 1 taps                             */
+    int32_t raw_dtype;     /* prc_raw_dtype of the input                                              */
+    int32_t nsel;          /* K: channels this call computes, 1 .. PRC_CHANNELIZE_MAX_SEL             */
+    int32_t reserved;      /* 0                                                                       */
+    int64_t start;         /* stream index of x[0]: a later block of a stream continues the phase     */
+} prc_channelize_desc;
+#define PRC_CHANNELIZE_DESC_SIZE_680 40u
+#define PRC_CHANNELIZE_MAX_CHAN 256
+#define PRC_CHANNELIZE_MAX_SEL 64
+#define PRC_CHANNELIZE_TILE_MAX_BYTES 163840   /* the LDS of a CU: a larger tile runs the direct form */
+int prc_channelize(const prc_channelize_desc* desc, const float* taps, const void* twiddles, const int32_t* channels, const void* x,
+                   int64_t n, void* out, int64_t out_stride, void* stream);
 
 /* ---- exact cross-ambiguity patches ("zoom") and sub-cell peak refinement ------------------------------------------------ */
 /* The un-decimated cross-ambiguity function on small lag x Doppler patches placed anywhere, at any Doppler spacing.  For a

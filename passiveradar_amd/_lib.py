@@ -23,7 +23,8 @@ CAF_MULTI_MODES = {"auto": CAF_MULTI_AUTO, "turns": CAF_MULTI_TURNS, "shared": C
 # prc_option
 (OPT_CAF_MULTI_MODE, OPT_CAF_GROUP_MB, OPT_LS_TEAM_PIECES, OPT_LS_TEAM_ALIGN, OPT_NLMS_WAVES, OPT_LS_CACHE_LIMIT_MB,
  OPT_NLMS_WG_WAVES, OPT_CAF_XCD_CONTIG, OPT_CAF_PAIR_FRAMES, OPT_FE_METHOD,
- OPT_CFAR_METHOD, OPT_MARKERS, OPT_FE_BALANCE, OPT_CAF_TEAM8, OPT_FE_FOLD, OPT_TBD_FRAMES, OPT_TBD_ROWS) = range(17)
+ OPT_CFAR_METHOD, OPT_MARKERS, OPT_FE_BALANCE, OPT_CAF_TEAM8, OPT_FE_FOLD, OPT_TBD_FRAMES, OPT_TBD_ROWS,
+ OPT_CHANNELIZE_FORM) = range(18)
 CAF_MAX_REFS = 8
 COMM_ID_BYTES = 128
 
@@ -120,6 +121,12 @@ class FirdecDesc(_Desc):
                 ("fc", C.c_double), ("fs", C.c_double), ("phase_offset", C.c_double)]
 
 
+class ChannelizeDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("nchan", C.c_int32), ("dec", C.c_int32), ("ntaps", C.c_int32), ("raw_dtype", C.c_int32),
+                ("nsel", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64)]
+
+
 class PatchDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
                 ("n", C.c_int64), ("frame_stride", C.c_int64), ("nframes", C.c_int32), ("nlags", C.c_int32),
@@ -203,6 +210,8 @@ ECHO_MAX_ATOMS, ECHO_MAX_REFINE = 32, 8                    # PRC_ECHO_MAX_ATOMS,
 ECHO_SKIPPED, ECHO_CLAMPED, ECHO_BROKE_DOWN = 1, 2, 4      # prc_echo_fit.flags
 
 FIRDEC_TILE_MAX_Q = 59       # PRC_FIRDEC_TILE_MAX_Q: the last q of decimate's filter that runs the LDS-tile form
+CHANNELIZE_MAX_CHAN, CHANNELIZE_MAX_SEL = 256, 64       # PRC_CHANNELIZE_MAX_CHAN, PRC_CHANNELIZE_MAX_SEL
+CHANNELIZE_TILE_MAX_BYTES = 163840                      # PRC_CHANNELIZE_TILE_MAX_BYTES
 
 # NumPy view of prc_strack_record (same layout as the ctypes mirror)
 STRACK_RECORD_DTYPE = np.dtype([("lock_mode", "<f8", (4,)), ("measurement", "<f8", (2,)),
@@ -327,6 +336,8 @@ _SIGNATURES = {
     "prc_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "prc_normalize_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "prc_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "prc_channelize": (C.c_int, [C.POINTER(ChannelizeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_int64, C.c_void_p]),
     "prc_xambg_patch_workspace_bytes": (C.c_int, [C.POINTER(PatchDesc), C.c_int32, C.POINTER(C.c_size_t)]),
     "prc_xambg_patch": (C.c_int, [C.POINTER(PatchDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),

@@ -8,11 +8,11 @@ import threading
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, engine, residence
 from ._lib import check, lib
 
 __all__ = ["xcorr", "frequency_shift", "deinterleave_IQ", "resample", "front_end", "find_channel_offset",
-           "decimate_iir", "decimate", "channel_preprocessing", "shift", "offset_compensation", "normalize"]
+           "decimate_iir", "decimate", "channel_preprocessing", "channelize", "shift", "offset_compensation", "normalize"]
 
 
 def _xcorr_equal_lengths(s1, s2, nlead, nlag):
@@ -221,11 +221,15 @@ def _decimate_taps(q):
 
 def _device_taps(q, device):
     """decimate's float32 taps on the device, from a small cache keyed by q"""
-    key = (device, q)
+    return _device_table((device, q), lambda: _decimate_taps(q))
+
+
+def _device_table(key, make):
+    """a small constant table (``make()``: a NumPy array) on the device, from the cache of the decimation taps"""
     with _taps_lock:
         buf = _taps.get(key)
         if buf is None:
-            h = _decimate_taps(q)
+            h = make()
             buf = _lib.DeviceBuffer(h.nbytes)
             buf.upload(h)
             _taps[key] = buf
@@ -355,6 +359,92 @@ def channel_preprocessing(sig, dec, fc, Fs):
     dr.upload(raw)
     _fir_decimate(dec, _lib.RAW_DTYPES[str(raw.dtype)], 1, fc, Fs, dr.ptr, raw.dtype.itemsize, n, 1, do.ptr, taps.ptr, None)
     return do.download((n_out,), np.complex64)
+
+
+def _twiddles(nchan):
+    """(cos, sin)(2 pi r / M), r < M: float64 on the host, rounded to float32 -- the only rotation channelize applies"""
+    ang = 2.0 * np.pi * np.arange(nchan, dtype=np.float64) / nchan
+    return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)
+
+
+def _channelize_input(sig):
+    """(raw dtype name, samples) of channelize's input: interleaved I,Q scalars as channel_preprocessing takes them (other
+    real dtypes are taken as float32, a trailing odd scalar is ignored) or a complex stream, taken as complex64"""
+    if sig.ndim != 1:
+        raise ValueError("channelize takes a one-dimensional array of interleaved I,Q scalars or a complex64 stream")
+    name = residence.dtype_name(sig)
+    if residence.iscomplex(sig):
+        if _lib.is_device_tensor(sig) and name != "complex64":
+            raise ValueError("channelize: a complex device tensor is complex64")
+        return "complex64", int(sig.shape[0])
+    if name not in _RAW_NUMPY:
+        if _lib.is_device_tensor(sig):
+            raise ValueError("channelize: a device tensor holds int8, uint8, int16 or float32 interleaved I,Q scalars, or complex64")
+        name = "float32"
+    return name, int(sig.shape[0]) // 2
+
+
+def channelize(sig, nchan, dec, channels=None, *, taps=None, start=0):
+    """Uniform polyphase filter bank: the channels ``channels`` (default: all, 0 .. nchan - 1) of ``nchan`` centred at
+    k Fs / nchan, low-passed by ``taps`` and decimated by ``dec``, out of ONE pass over the raw recording; complex64 of shape
+    (K, ceil(n / dec)).  With c = (L - 1) / 2 and x[start + .] the stream,
+
+        y[i][j] = sum_t taps[t] x[j dec + c - t] exp(-2 pi i ((k_i (start + j dec + c - t)) mod nchan) / nchan)
+
+    -- with the default taps (decimate's firwin(20 dec + 1, 1 / dec), float32) row i is
+    ``channel_preprocessing(sig, dec, -k_i Fs / nchan, Fs)`` with an exact phase: the exponent is an integer reduced modulo
+    nchan and the rotation a table of nchan float32 twiddles, so ``start`` = 2^40 is as accurate as 0 and a later block of a
+    stream, passed with its own ``start``, continues the earlier one.  dec need not equal, divide or be divided by nchan.
+    ``sig``: interleaved I,Q scalars typed as channel_preprocessing takes them, or a complex64 stream; NumPy, or a torch
+    device tensor, which is read in place on torch's current stream and gives a device tensor.  A channel is an integer in
+    [-nchan / 2, nchan): k and k - nchan are the same; duplicates are allowed and the bits of a row do not depend on the
+    other rows asked for.  ``taps``: real, odd length."""
+    M, D, start = operator.index(nchan), operator.index(dec), operator.index(start)
+    if not 2 <= M <= _lib.CHANNELIZE_MAX_CHAN:
+        raise ValueError(f"channelize: nchan = {M} outside 2 .. {_lib.CHANNELIZE_MAX_CHAN}")
+    if taps is None:
+        if D < 2:
+            raise ValueError("channelize: dec must be 2 or more with the default taps (pass taps for dec = 1)")
+        h, L = None, 20 * D + 1
+    else:
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        if h.ndim != 1 or h.shape[0] % 2 == 0:
+            raise ValueError("channelize: taps are one-dimensional, of odd length")
+        if D < 1:
+            raise ValueError("channelize: dec must be a positive integer")
+        L = h.shape[0]
+    if not -2 ** 63 <= start < 2 ** 63:
+        raise ValueError("channelize: start is an int64 stream index")
+    if channels is None:
+        ch = np.arange(M, dtype=np.int32)
+    else:
+        ch = np.asarray(channels)
+        if ch.ndim != 1 or (ch.size and ch.dtype.kind not in "iu"):
+            raise ValueError("channelize: channels is a one-dimensional list of integers")
+        if ch.size and (np.any(2 * ch.astype(np.int64) < -M) or np.any(ch.astype(np.int64) >= M)):
+            raise ValueError(f"channelize: a channel outside [-{M}/2, {M})")
+        ch = ch.astype(np.int32)
+    side = residence.of(sig)
+    if not side.torch:
+        sig = np.asarray(sig)
+    name, n = _channelize_input(sig)
+    K, n_out = int(ch.shape[0]), -(-n // D)
+    if n == 0 or K == 0:
+        return side.nothing((K, n_out), np.complex64)
+    with side.device():
+        x = side.put("cz_x", sig, name)
+        dev = sig.device.index if side.torch else _lib.current_device()
+        dtaps = _device_taps(D, dev) if h is None else side.put("cz_taps", h, np.float32)
+        dtw = _device_table((dev, "twiddles", M), lambda: _twiddles(M))
+        dch = side.put("cz_ch", ch, np.int32)
+        out = side.empty("cz_out", (K, n_out), np.complex64)
+        d = _lib.ChannelizeDesc()
+        d.nchan, d.dec, d.ntaps, d.raw_dtype, d.start = M, D, L, _lib.RAW_DTYPES[name], start
+        for k0 in range(0, K, _lib.CHANNELIZE_MAX_SEL):              # 64 rows per launch
+            d.nsel = min(_lib.CHANNELIZE_MAX_SEL, K - k0)
+            check(lib().prc_channelize(C.byref(d), dtaps.ptr, dtw.ptr, dch.ptr + 4 * k0, x.ptr, n, out.ptr + 8 * k0 * n_out, n_out,
+                                       side.stream))
+    return side.result(out, (K, n_out), np.complex64)
 
 
 def shift(x, n):
