@@ -36,7 +36,12 @@
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
  *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots, tests/test_gpu_tbd_bounds.py prc_tbd and
- *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel, tests/test_gpu_channelize_bounds.py prc_channelize).
+ *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel, tests/test_gpu_channelize_bounds.py prc_channelize;
+ *     tests/test_gpu_far_blocks.py holds the strided entry points to it with the blocks more than 4 GiB apart and the dense
+ *     stacks with their last frame beyond 2^32 bytes, tests/test_gpu_long_streams.py the whole-recording entry points on
+ *     streams past 2^31 samples and 2^32 bytes).  Every length, stride and step declared int64_t either works at any such
+ *     distance or is refused before any launch with a status and a message naming the size; each entry point's comment says
+ *     which, tests/test_limits_host.py holds every limit, DESIGN.md section 26 has the audit.
  */
 #ifndef PRCORE_H
 #define PRCORE_H
@@ -210,6 +215,15 @@ typedef struct prc_caf_desc {
 
 typedef struct prc_caf_plan prc_caf_plan;
 
+/* Limits: the segment kernels address a frame with 32-bit byte offsets, so a frame and one transform of slack must lie below
+ * 4 GiB: n <= PRC_CAF_MAX_N, else PRC_ESHAPE (the message names n and the limit), checked before anything is allocated.
+ * frame_stride is a 64-bit element count with no such limit: frames may lie any distance apart.  The direct and the
+ * 1024-point method, and any method with the rocFFT Doppler path, put the frames of a call into a grid dimension:
+ * max_frames <= PRC_MAX_BATCH there, else PRC_ESHAPE (the 4096-point method with the column Doppler kernel takes any count).
+ * The limit on n holds for every method: the direct kernels index with 64 bits, but have never been run or measured
+ * beyond it, and 2^16 samples of slack (sixteen 4096-point pieces) keep every prefetch of a piece past the end in range. */
+#define PRC_MAX_BATCH 65535                  /* blocks / frames / channels one launch takes as a grid dimension */
+#define PRC_CAF_MAX_N ((int64_t)536805376)   /* 2^29 - 2^16 complex64 samples per CPI */
 int prc_caf_plan_create(prc_caf_plan** plan, const prc_caf_desc* desc);
 int prc_caf_plan_destroy(prc_caf_plan* plan);
 /* Which kernels the plan resolved AUTO to (prc_caf_method / prc_doppler_method values). */
@@ -273,6 +287,13 @@ typedef struct prc_ls_desc {
 
 typedef struct prc_ls_plan prc_ls_plan;
 
+/* Limits: the FFT kernels address a block with 32-bit byte offsets, so a block and one transform of slack must lie below
+ * 4 GiB: n <= PRC_LS_MAX_N, else PRC_ESHAPE; the blocks of a call are one grid dimension: max_blocks <= PRC_MAX_BATCH, else
+ * PRC_ESHAPE (each message names the value and the limit); both are checked before anything is allocated.  stride and
+ * out_stride of prc_ls_execute are 64-bit element counts with no such limit: blocks may lie any distance apart.  The limit
+ * on n holds for every method, the time-domain kernels (method 1, or more taps than the FFT kernels carry) included: they
+ * index with 64 bits but have never been run or measured beyond it, and a plan is then not a different object per method. */
+#define PRC_LS_MAX_N ((int64_t)536805376)    /* 2^29 - 2^16 complex64 samples per block */
 int prc_ls_plan_create(prc_ls_plan** plan, const prc_ls_desc* desc);
 int prc_ls_plan_destroy(prc_ls_plan* plan);
 
@@ -329,7 +350,8 @@ int prc_nlms_execute(const void* ref, const void* srv, int64_t n, int64_t stride
  * returns with the sweeps complete and the last kernels (taps, FIR) enqueued on `stream`.  Results are bit-identical from
  * run to run and do not depend on which other blocks share the call.
  * Limits: 1 <= T < n, T <= 4096, stride and out_stride >= n.  Anything else, a null ref / srv / out / workspace or a
- * misaligned workspace: PRC_EINVAL. */
+ * misaligned workspace: PRC_EINVAL.  PRC_ESHAPE: n >= 2^31 or nblocks > PRC_MAX_BATCH (the message names the value and the
+ * limit; prc_ls_svd_workspace_bytes refuses the same).  stride and out_stride have no upper limit. */
 int prc_ls_svd_workspace_bytes(int64_t n, int32_t filter_len, int32_t peek, int32_t nblocks, size_t* bytes);
 int prc_ls_svd_execute(const void* ref, const void* srv, int64_t n, int64_t stride, int32_t filter_len, int32_t peek,
                        double rcond /* < 0: the default above */, int32_t nblocks, void* out, int64_t out_stride,
@@ -364,7 +386,9 @@ int prc_ls_svd_get_profile(double* ms /* [4] */, int32_t* sweeps);
  * The call neither allocates nor synchronises, has a fixed number of launches and reads nothing back: it can be captured
  * into a graph.  Results are bit-identical from run to run and do not depend on which other blocks share the call.
  * Limits: 1 <= T < n, 1 <= nbins <= 8, nbins * T <= 4096, stride and out_stride >= n.  Anything else, a null ref / srv / out /
- * doppler_bins_host / workspace, a misaligned workspace, a negative or non-finite reg or a zero sample_rate: PRC_EINVAL. */
+ * doppler_bins_host / workspace, a misaligned workspace, a negative or non-finite reg or a zero sample_rate: PRC_EINVAL.
+ * PRC_ESHAPE: n >= 2^31 or nblocks > PRC_MAX_BATCH (the message names the value and the limit; prc_eca_workspace_bytes refuses
+ * the same).  stride and out_stride have no upper limit. */
 int prc_eca_workspace_bytes(int64_t n, int32_t filter_len, int32_t peek, int32_t nbins, int32_t nblocks, size_t* bytes);
 int prc_eca_execute(const void* ref, const void* srv, int64_t n, int64_t stride, int32_t filter_len, int32_t peek,
                     double sample_rate, const double* doppler_bins_host, int32_t nbins, double reg, int32_t nblocks,
@@ -394,7 +418,8 @@ int prc_gal_execute(const void* ref, const void* srv, int64_t n, int64_t stride,
                     void* k_out, void* h_out, int32_t nstreams, void* workspace, void* stream);
 
 /* ---- helpers that sit on the path (signal_utils.py) ---------------------------------- */
-/* xcorr (:29-32): z[i] = sum_n s1[n] conj(s2[n-(i-nlead)]), i = 0..nlag+nlead; complex64 out. */
+/* xcorr (:29-32): z[i] = sum_n s1[n] conj(s2[n-(i-nlead)]), i = 0..nlag+nlead; complex64 out.  n is a 64-bit count: whole
+ * recordings run (blocks of 4096 samples are one grid dimension: PRC_ESHAPE for n > 4096 (2^31 - 1), with n in the message). */
 int prc_xcorr(const void* s1, const void* s2, int64_t n, int32_t nlead, int32_t nlag,
               void* out, void* stream);
 /* frequency_shift (:24-27): y[n] = x[n] exp(j(fl32 phase ramp + phase_offset)). */
@@ -422,6 +447,9 @@ typedef struct prc_frontend_desc {
 #define PRC_FRONTEND_DESC_SIZE_600 48u
 
 typedef struct prc_frontend_plan prc_frontend_plan;
+/* Limits, checked before anything is allocated: n_in < 2^30 (PRC_EINVAL); the blocks of a call are one grid dimension:
+ * max_blocks <= PRC_MAX_BATCH, else PRC_ESHAPE (the message names max_blocks and the limit).  raw_stride and out_stride are
+ * 64-bit element counts with no upper limit. */
 int prc_frontend_plan_create(prc_frontend_plan** plan, const prc_frontend_desc* desc);
 int prc_frontend_plan_destroy(prc_frontend_plan* plan);
 int prc_frontend_out_len(const prc_frontend_plan* plan, int64_t* n_out);   /* ceil(n_in*up/down) */
@@ -455,7 +483,9 @@ int prc_frequency_shift_phases(const void* x, void* y, int64_t n, double fc, dou
 /* ---- CFAR_2D (SURVEY 8f "next" #3): target_detection.py:683-703 ------------------------------ */
 /* X: float32 [nframes][H][W] (|xambg|, H = Doppler rows, W = range columns); out float32 same shape:
  * the CFAR ratio, or 0/1 where ratio > thresh when use_thresh != 0.  Wrap-around box filter of width fw
- * with the (gw+1)^2 guard hole and the 1/(fw^2-gw^2) gain of the reference, normalised by mean|X|. */
+ * with the (gw+1)^2 guard hole and the 1/(fw^2-gw^2) gain of the reference, normalised by mean|X|.  The frames are a grid
+ * dimension: nframes > PRC_MAX_BATCH is PRC_ESHAPE (prc_cfar2d_c64 too), checked before anything is allocated; frame f
+ * is read and written at the 64-bit offset f H W, so a stack may be longer than 2^32 bytes. */
 int prc_cfar2d(const float* X, int32_t H, int32_t W, int32_t fw, int32_t gw, int32_t use_thresh,
                float thresh, float* out, int32_t nframes, void* stream);
 /* CFAR_2D(np.abs(X), fw, gw[, thresh]) as range_doppler_plot.py:56-57 calls it: X = the complex64 range-Doppler maps
@@ -791,7 +821,9 @@ int prc_strack_run(const prc_strack_desc* desc, const void* frames, int32_t nfra
  * in_dtype; out: DEVICE [k_count][frame_elems] of out_dtype (float32: the float64 sum rounded once).  The powers travel in
  * the kernel arguments, 256 per launch; with more terms the launches chain through a float64 `out`, so a float32 out
  * takes at most 256 terms.  Neither allocates nor synchronises.  PRC_EINVAL for bad dtypes, negative sizes, a null
- * pointer, a frame k >= nframes that would be read, or more than 256 terms with a float32 out. */
+ * pointer, a frame k >= nframes that would be read, more than 256 terms with a float32 out, frame_elems above
+ * 256 (2^31 - 1) or k_count above 8 PRC_MAX_BATCH (the message names the value and the limit).  frame_elems and every
+ * element index k * frame_elems + e are 64-bit: a stack may be longer than 2^32 bytes. */
 #define PRC_PERSISTENCE_TERMS_PER_LAUNCH 256
 int prc_persistence(const void* frames, int32_t in_dtype, int64_t frame_elems, int32_t nframes, int32_t k_first,
                     int32_t k_count, int32_t hold, double decay, void* out, int32_t out_dtype, void* stream);
@@ -840,7 +872,8 @@ int prc_display_rgba(const void* frames, int32_t dtype, int32_t H, int32_t W, in
  * zero imaginary part.  Three kernels on `stream`; neither allocates nor synchronises.  `workspace`: DEVICE,
  * prc_welch_workspace_bytes bytes, not shared by calls in flight (it holds the twiddles and the per-workgroup sums).
  * PRC_EINVAL: nfft not a power of two in 64 .. 8192, noverlap outside [0, nfft), navg < 0, a detrend other than 0 / 1, a
- * bad in_dtype, step < 1, n < 1, nch < 1, null pointers (y excepted), a bad descriptor header; PRC_ESHAPE: navg > nseg.
+ * bad in_dtype, step < 1, n < 1, nch < 1, null pointers (y excepted), a bad descriptor header; PRC_ESHAPE: navg > nseg;
+ * PRC_EUNSUPPORTED: nch * rows * (workgroups per row, at most 64) above 2^31 - 1.  n, stride and every sample index are 64-bit.
  * prc_welch_rows and prc_welch_workspace_bytes are host arithmetic and need no device. */
 typedef struct prc_welch_desc {
     uint32_t struct_size;  /* sizeof(prc_welch_desc) as the host compiled it (see Conventions)             */

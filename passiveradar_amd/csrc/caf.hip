@@ -112,6 +112,9 @@ extern "C" int prc_caf_plan_create(prc_caf_plan** plan, const prc_caf_desc* host
                 "prc_caf_plan_create: freq_bins (%d) exceeds the CPI length (%lld): the reference "
                 "divides by q = int(n/freq_bins) = 0", d->freq_bins, (long long)d->n);
     PRC_REQUIRE(d->range_bins < d->n, PRC_EINVAL, "prc_caf_plan_create: range_bins >= n");
+    // the segment kernels narrow n and n_valid to int and build buffer descriptors of n_valid * 8 bytes with 32-bit lane offsets
+    PRC_REQUIRE(d->n <= PRC_CAF_MAX_N, PRC_ESHAPE, "prc_caf_plan_create: n = %lld exceeds the limit of %lld samples per CPI (PRC_CAF_MAX_N)",
+                (long long)d->n, (long long)PRC_CAF_MAX_N);
     PRC_REQUIRE(d->ntaps == 0 || d->taps_host, PRC_EINVAL, "prc_caf_plan_create: ntaps without taps");
     // every argument check comes before the plan exists (a failed check after `new` leaked it)
     PRC_REQUIRE(d->multi >= PRC_CAF_MULTI_AUTO && d->multi <= PRC_CAF_MULTI_PAIRS, PRC_EINVAL,
@@ -155,6 +158,14 @@ extern "C" int prc_caf_plan_create(prc_caf_plan** plan, const prc_caf_desc* host
                       "and surfaces below 2^32 / 3 bytes (got %d x %d)", d->freq_bins, d->range_bins + 1);
         delete p;
         return PRC_EUNSUPPORTED;
+    }
+    // the direct and 1024-point segment kernels and the rocFFT Doppler path put the frames of a group into a grid dimension
+    // (the 4096-point kernels with the column Doppler kernel spread them over grid.x); nothing is allocated yet
+    if ((p->method != PRC_CAF_FFT4096 || p->doppler == PRC_DOPPLER_ROCFFT) && d->max_frames > PRC_MAX_BATCH) {
+        prc_set_error("prc_caf_plan_create: max_frames = %d exceeds the limit of %d frames (PRC_MAX_BATCH) of method %d with "
+                      "Doppler method %d", d->max_frames, PRC_MAX_BATCH, p->method, p->doppler);
+        delete p;
+        return PRC_ESHAPE;
     }
     p->multi = d->multi != PRC_CAF_MULTI_AUTO ? d->multi : (int)prc_opt(PRC_OPT_CAF_MULTI_MODE);
     if (p->multi == PRC_CAF_MULTI_AUTO) {

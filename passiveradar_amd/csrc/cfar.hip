@@ -155,6 +155,9 @@ __global__ __launch_bounds__(256) void cfar_sep_kernel(const TIn* __restrict__ X
 template <typename TIn>
 static int cfar_run(const TIn* X, int32_t H, int32_t W, int32_t fw, int32_t gw, int32_t use_thresh,
                     float thresh, float* out, int32_t nframes, void* stream_) {
+    // the frames are a grid dimension of all three kernels; the size check stands before the scratch is grown
+    PRC_REQUIRE(nframes <= PRC_MAX_BATCH, PRC_ESHAPE, "prc_cfar2d: nframes = %d exceeds the limit of %d frames (PRC_MAX_BATCH)", nframes,
+                PRC_MAX_BATCH);
     PRC_REQUIRE(X && out, PRC_EINVAL, "prc_cfar2d: null argument");
     PRC_REQUIRE(H > 0 && W > 0 && fw > 0 && gw >= 0 && nframes > 0, PRC_EINVAL, "prc_cfar2d: bad size");
     PRC_REQUIRE(fw * fw != gw * gw, PRC_EINVAL, "prc_cfar2d: fw^2 == gw^2 divides by zero (as in the reference)");

@@ -444,6 +444,10 @@ static int eca_check_sizes(const char* who, int64_t n, int32_t filter_len, int32
     PRC_REQUIRE(filter_len >= 0 && peek >= 0 && nblocks > 0 && n > 0, PRC_EINVAL,
                 "%s: non-positive size (n %lld, filter_len %d, peek %d, nblocks %d)", who, (long long)n, filter_len, peek, nblocks);
     PRC_REQUIRE(nbins >= 1 && nbins <= ECA_MAX_BINS, PRC_EINVAL, "%s: %d Doppler bins, need 1 .. %d", who, nbins, ECA_MAX_BINS);
+    PRC_REQUIRE(n < ((int64_t)1 << 31), PRC_ESHAPE, "%s: n = %lld exceeds the limit of %lld samples per block", who, (long long)n,
+                (long long)(((int64_t)1 << 31) - 1));
+    PRC_REQUIRE(nblocks <= PRC_MAX_BATCH, PRC_ESHAPE, "%s: nblocks = %d exceeds the limit of %d blocks (PRC_MAX_BATCH)", who, nblocks,
+                PRC_MAX_BATCH);
     const int64_t T = (int64_t)filter_len + peek;
     PRC_REQUIRE(T >= 1 && T < n && T * nbins <= ECA_MAX_UNKNOWNS, PRC_EINVAL,
                 "%s: filter_len + peek = %lld taps, need 1 <= taps < n (%lld) and nbins * taps <= %d", who, (long long)T, (long long)n,

@@ -647,7 +647,10 @@ extern "C" int prc_frontend_plan_create(prc_frontend_plan** plan, const prc_fron
     if (int rc = prc_take_desc(&mine, host_desc, PRC_FRONTEND_DESC_SIZE_600, "prc_frontend_plan_create", "prc_frontend_desc")) return rc;
     const prc_frontend_desc* d = &mine;
     PRC_REQUIRE(d->n_in > 1 && d->n_in < ((int64_t)1 << 30) && d->up > 0 && d->down > 0 && d->ntaps > 0 && d->taps_host &&
-                d->max_blocks > 0, PRC_EINVAL, "prc_frontend_plan_create: bad size (blocks of 2 .. 2^30 complex samples)");
+                d->max_blocks > 0, PRC_EINVAL, "prc_frontend_plan_create: bad size (n_in = %lld: blocks of 2 .. 2^30 - 1 complex samples)",
+                (long long)d->n_in);
+    PRC_REQUIRE(d->max_blocks <= PRC_MAX_BATCH, PRC_ESHAPE, "prc_frontend_plan_create: max_blocks = %d exceeds the limit of %d blocks (PRC_MAX_BATCH)",
+                d->max_blocks, PRC_MAX_BATCH);
     PRC_REQUIRE(d->raw_dtype >= PRC_RAW_I8 && d->raw_dtype <= PRC_RAW_C64, PRC_EINVAL,
                 "prc_frontend_plan_create: unknown raw dtype %d", d->raw_dtype);
     prc_frontend_plan* p = new prc_frontend_plan();

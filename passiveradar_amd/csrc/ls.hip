@@ -1072,10 +1072,16 @@ static int ls_plan_create_impl(prc_ls_plan** plan, const prc_ls_desc* d, bool al
     PRC_REQUIRE(plan && d, PRC_EINVAL, "prc_ls_plan_create: null argument");
     PRC_REQUIRE(d->n > 0 && d->filter_len > 0 && d->peek >= 0 && d->max_blocks > 0, PRC_EINVAL,
                 "prc_ls_plan_create: non-positive size");
-    PRC_REQUIRE(d->method >= 0 && d->method <= 4, PRC_EINVAL, "prc_ls_plan_create: method %d", d->method);
     const int T = d->filter_len + d->peek;
     PRC_REQUIRE(T < d->n, PRC_EINVAL, "prc_ls_plan_create: filter_len+peek (%d) >= n (%lld)", T,
                 (long long)d->n);
+    // the FFT kernels narrow n to int and build buffer descriptors of (n - peek) * 8 bytes with 32-bit lane offsets; every
+    // size check comes before the plan exists
+    PRC_REQUIRE(d->n <= PRC_LS_MAX_N, PRC_ESHAPE, "prc_ls_plan_create: n = %lld exceeds the limit of %lld samples per block (PRC_LS_MAX_N)",
+                (long long)d->n, (long long)PRC_LS_MAX_N);
+    PRC_REQUIRE(d->max_blocks <= PRC_MAX_BATCH, PRC_ESHAPE, "prc_ls_plan_create: max_blocks = %d exceeds the limit of %d blocks (PRC_MAX_BATCH)",
+                d->max_blocks, PRC_MAX_BATCH);
+    PRC_REQUIRE(d->method >= 0 && d->method <= 4, PRC_EINVAL, "prc_ls_plan_create: method %d", d->method);
     prc_ls_plan* p = new prc_ls_plan();
     p->desc = *d;
     p->T = T;
@@ -1505,8 +1511,10 @@ __global__ void xcorr_reduce_kernel(const float2* __restrict__ partial, int nblk
 extern "C" int prc_xcorr(const void* s1, const void* s2, int64_t n, int32_t nlead, int32_t nlag,
                          void* out, void* stream_) {
     PRC_RANGE("prc_xcorr");
-    PRC_REQUIRE(s1 && s2 && out, PRC_EINVAL, "prc_xcorr: null argument");
     PRC_REQUIRE(n > 0 && nlead >= 0 && nlag >= 0, PRC_EINVAL, "prc_xcorr: bad size");
+    PRC_REQUIRE(ceil_div64(n, LSC_BLK) <= (int64_t)0x7fffffff, PRC_ESHAPE, "prc_xcorr: n = %lld exceeds the limit of %lld samples",
+                (long long)n, (long long)LSC_BLK * 0x7fffffff);
+    PRC_REQUIRE(s1 && s2 && out, PRC_EINVAL, "prc_xcorr: null argument");
     // lags beyond the signal length are legal (signal_utils.py:29-32 pads s2 by nlag / nlead zeros): their sums are 0
     hipStream_t stream = (hipStream_t)stream_;
     const int nblk = (int)ceil_div64(n, LSC_BLK);

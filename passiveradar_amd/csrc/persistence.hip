@@ -83,6 +83,10 @@ extern "C" int prc_persistence(const void* frames, int32_t in_dtype, int64_t fra
                 "prc_persistence: frame_elems = %lld, nframes = %d, k_count = %d", (long long)frame_elems, nframes,
                 k_count);
     if (frame_elems == 0 || k_count == 0) return PRC_OK;
+    PRC_REQUIRE((frame_elems + PT - 1) / PT <= 0x7fffffff, PRC_EINVAL, "prc_persistence: frame_elems = %lld exceeds the limit of %lld",
+                (long long)frame_elems, (long long)PT * 0x7fffffff);
+    PRC_REQUIRE((k_count + PERS_KB - 1) / PERS_KB <= PRC_MAX_BATCH, PRC_EINVAL, "prc_persistence: k_count = %d exceeds the limit of %d frames",
+                k_count, PERS_KB * PRC_MAX_BATCH);
     PRC_REQUIRE(out, PRC_EINVAL, "prc_persistence: null out");
     PRC_REQUIRE((int64_t)k_first + k_count - 1 <= 0x7fffffff, PRC_EINVAL, "prc_persistence: k_first + k_count too large");
     const int64_t k_last = (int64_t)k_first + k_count - 1;
@@ -96,7 +100,6 @@ extern "C" int prc_persistence(const void* frames, int32_t in_dtype, int64_t fra
     PRC_REQUIRE(out_dtype == PRC_REAL_F64 || nterms <= PERS_TERMS, PRC_EINVAL,
                 "prc_persistence: %lld terms with a float32 out: at most %d (the launches chain through a float64 out)",
                 (long long)nterms, PERS_TERMS);
-    PRC_REQUIRE((frame_elems + PT - 1) / PT <= 0x7fffffff, PRC_EINVAL, "prc_persistence: frame_elems too large");
     PersArgs a;
     a.elems = frame_elems;
     a.k_first = k_first;

@@ -396,15 +396,16 @@ extern "C" int prc_welch(const prc_welch_desc* desc, const void* x, const void* 
     const int rc = welch_check(&d, desc, n, &sh, "prc_welch");
     if (rc != PRC_OK) return rc;
     PRC_REQUIRE(nch >= 1, PRC_EINVAL, "prc_welch: nch = %d", nch);
-    PRC_REQUIRE(x && window && out && workspace, PRC_EINVAL, "prc_welch: null argument");
-    PRC_REQUIRE(((uintptr_t)workspace & 7u) == 0 && ((uintptr_t)out & 7u) == 0, PRC_EINVAL,
-                "prc_welch: out and workspace need 8-byte alignment");
-    PRC_REQUIRE(nch == 1 || stride >= 0, PRC_EINVAL, "prc_welch: stride = %lld", (long long)stride);
     const int64_t nrows = (int64_t)nch * sh.rows;
     const Split sp = welch_split(sh.spr);
     const int64_t wgs = nrows * sp.W;
     PRC_REQUIRE(wgs <= (int64_t)0x7fffffff && nrows <= (int64_t)0x7fffffff, PRC_EUNSUPPORTED,
-                "prc_welch: %lld output rows are more than one launch takes", (long long)nrows);
+                "prc_welch: %lld output rows in %lld workgroups are more than one launch takes (limit %lld)", (long long)nrows,
+                (long long)wgs, (long long)0x7fffffff);
+    PRC_REQUIRE(x && window && out && workspace, PRC_EINVAL, "prc_welch: null argument");
+    PRC_REQUIRE(((uintptr_t)workspace & 7u) == 0 && ((uintptr_t)out & 7u) == 0, PRC_EINVAL,
+                "prc_welch: out and workspace need 8-byte alignment");
+    PRC_REQUIRE(nch == 1 || stride >= 0, PRC_EINVAL, "prc_welch: stride = %lld", (long long)stride);
     hipStream_t st = (hipStream_t)stream;
     const int N = d.nfft;
     float2* tw = (float2*)workspace;

@@ -37,6 +37,94 @@ def test_python_binding_matches_header():
     _lib.lib()      # argtypes/restype set for every symbol
 
 
+def declared_prototypes():
+    """name -> [(C type, parameter name)] of every function the header declares"""
+    text = open(os.path.join(REPO, "include", "prcore.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    protos = {}
+    for name, params in re.findall(r"\b(prc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        plist = []
+        for p in (q.strip() for q in params.split(",")):
+            if p in ("void", ""):
+                continue
+            m = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", p)
+            plist.append((re.sub(r"\s+", " ", m.group(1)).replace(" *", "*").strip(), m.group(2)))
+        protos[name] = plist
+    return protos
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+            "double": ctypes.c_double, "float": ctypes.c_float}
+
+
+def test_argtypes_match_the_prototypes_by_name_and_position():
+    """every parameter of every prototype against _lib._SIGNATURES: the count, every scalar exactly (an int64_t length or
+    stride bound as c_int32 would truncate past 2^31 without an error), and a pointer as a pointer; an int64_t* is
+    POINTER(c_int64) or an untyped address"""
+    from passiveradar_amd import _lib
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols()
+    bad, n64 = [], 0
+    for name, params in protos.items():
+        args = _lib._SIGNATURES[name][1]
+        if len(args) != len(params):
+            bad.append(f"{name}: {len(params)} parameters declared, {len(args)} bound")
+            continue
+        for k, ((ctype, pname), bound) in enumerate(zip(params, args)):
+            if ctype.endswith("*"):
+                ok = bound is ctypes.c_void_p or bound is ctypes.c_char_p or hasattr(bound, "_type_") and not isinstance(bound._type_, str)
+                if ctype.replace("const ", "") == "int64_t*" and bound is not ctypes.c_void_p:
+                    ok = bound._type_ is ctypes.c_int64
+            else:
+                ok = bound is _SCALARS[ctype.replace("const ", "")]
+                n64 += ctype == "int64_t"
+            if not ok:
+                bad.append(f"{name}: parameter {k} `{ctype} {pname}` is bound as {bound.__name__}")
+    assert not bad, bad
+    assert n64 >= 40                                       # the lengths, strides and steps this is about were seen
+
+
+def test_int64_descriptor_fields_are_c_int64():
+    """the same for the descriptor structs: every int64_t field of a struct the header declares is a c_int64 field of that
+    name in its ctypes mirror"""
+    from passiveradar_amd import _lib
+    text = open(os.path.join(REPO, "include", "prcore.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    mirrors = {"prc_caf_desc": _lib.CafDesc, "prc_ls_desc": _lib.LsDesc, "prc_frontend_desc": _lib.FrontendDesc,
+               "prc_channelize_desc": _lib.ChannelizeDesc, "prc_patch_desc": _lib.PatchDesc, "prc_echo_desc": _lib.EchoDesc,
+               "prc_track_cand": _lib.TrackCand}
+    seen = set()
+    for struct, body in re.findall(r"typedef struct (prc_\w+) \{(.*?)\}", text, flags=re.S):
+        fields = [n for decl in re.findall(r"\bint64_t ([^;]*);", body) for n in (x.strip().split("[")[0] for x in decl.split(","))]
+        if not fields:
+            continue
+        if struct == "prc_strack_record":                   # an array field: the NumPy view carries it
+            assert _lib.STRACK_RECORD_DTYPE["measurement_idx"].base == "<i8"
+            continue
+        assert struct in mirrors, f"{struct} has int64_t fields and no mirror listed here"
+        types = dict(mirrors[struct]._fields_)
+        for f in fields:
+            assert types[f] is ctypes.c_int64, (struct, f)
+        seen.add(struct)
+    assert seen == set(mirrors)
+
+
+def test_front_doors_pass_sizes_without_an_int32_conversion():
+    """a narrow check of the one idiom a front door would most likely use: no `np.int32(...)`, `c_int32(...)` or `c_int(...)`
+    call in the package wraps an expression that names a length, stride, step, row count or shift.  It does not see
+    `.astype(np.int32)`, int32 tensors or masks; what binds the sizes is the argtypes test above, which makes ctypes
+    convert every Python int to 64 bits itself"""
+    pkg = os.path.join(REPO, "passiveradar_amd")
+    narrow = re.compile(r"(?:np\.int32|c_int32|c_int)\(\s*(?!\)|0\)|-1\))([^)]*)\)")
+    for fn in sorted(os.listdir(pkg)):
+        if fn.endswith(".py"):
+            for k, line in enumerate(open(os.path.join(pkg, fn)), 1):
+                for arg in narrow.findall(line):
+                    assert not re.search(r"\b(n|n\w*|len\w*|\w*stride|\w*step|rows|row_bytes|shift|start|frame_elems|nl)\b", arg), \
+                        f"{fn}:{k}: {line.strip()}"
+
+
 def test_no_cpu_fallback_without_gpu():
     """On a box without a GPU the product path must raise, never compute on the CPU."""
     import numpy as np

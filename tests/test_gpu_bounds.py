@@ -104,17 +104,17 @@ NF = 3
 
 
 @functools.lru_cache(maxsize=4)
-def _caf_scene(n, n_valid, R, overlap, seed, nref):
-    m = n // 2 * (NF + 1) if overlap else n_valid * NF
+def _caf_scene(n, n_valid, R, overlap, seed, nref, nf=NF):
+    m = n // 2 * (nf + 1) if overlap else n_valid * nf
     refs, srv = scene.make_multi_scene(m, 1e4, max(min(R, 200), 1), [seed + 13 * i for i in range(nref)])
     if overlap:
         return [r[None] for r in refs], srv[None]
-    return [r.reshape(NF, n_valid) for r in refs], srv.reshape(NF, n_valid)
+    return [r.reshape(nf, n_valid) for r in refs], srv.reshape(nf, n_valid)
 
 
-def _caf_data(n, n_valid, R, mode, seed, nref=1):
-    """``mode`` = "overlap": one stream, frames at n/2; else (a gap) distinct frames [NF, n_valid] cut from one scene"""
-    return _caf_scene(n, n_valid, R, mode == "overlap", seed, nref)
+def _caf_data(n, n_valid, R, mode, seed, nref=1, nf=NF):
+    """``mode`` = "overlap": one stream, frames at n/2; else (a gap) distinct frames [nf, n_valid] cut from one scene"""
+    return _caf_scene(n, n_valid, R, mode == "overlap", seed, nref, nf)
 
 
 def _caf_in(x, n, n_valid, mode):
@@ -128,24 +128,25 @@ def _caf_frame(x, n, mode, b):
     return x[0, b * (n // 2):b * (n // 2) + n] if mode == "overlap" else x[b]
 
 
-def _caf_check(plan, n, R, F, mode, win, n_valid, seed, via="execute", oracle=True):
-    refs, srv = _caf_data(n, n_valid, R, mode, seed)
+def _caf_check(plan, n, R, F, mode, win, n_valid, seed, via="execute", oracle=True, nf=NF):
+    """``nf`` frames of a plan made for at least as many (tests/test_gpu_far_blocks.py runs two, 4 GiB apart)"""
+    refs, srv = _caf_data(n, n_valid, R, mode, seed, 1, nf)
     ins = {"ref": _caf_in(refs[0], n, n_valid, mode), "srv": _caf_in(srv, n, n_valid, mode)}
     if win is not None:
         ins["win"] = guard.In(_dev(win.astype(np.float32))[None])
-    outs = {"out": guard.Out(1, NF * F * (R + 1), torch.complex64)}
+    outs = {"out": guard.Out(1, nf * F * (R + 1), torch.complex64)}
 
     def run(a, s):
         stride = n // 2 if mode == "overlap" else s["ref"]
         if via == "execute":
-            plan.execute(a["ref"], a["srv"], a["out"], NF, stride, n_valid, a.get("win"))
+            plan.execute(a["ref"], a["srv"], a["out"], nf, stride, n_valid, a.get("win"))
         else:
-            plan.execute_segments(a["ref"], a["srv"], NF, stride, n_valid, a.get("win"))
-            plan.execute_doppler(a["out"], NF)
+            plan.execute_segments(a["ref"], a["srv"], nf, stride, n_valid, a.get("win"))
+            plan.execute_doppler(a["out"], nf)
         _sync()
-    got = _host(guard.check(run, ins, outs).tight["out"]).reshape(NF, F, R + 1)
+    got = _host(guard.check(run, ins, outs).tight["out"]).reshape(nf, F, R + 1)
     if oracle:
-        b = NF - 1
+        b = nf - 1
         exp = O.fast_xambg(_caf_frame(refs[0], n, mode, b), _caf_frame(srv, n, mode, b), R, F, n, win,
                            plan._taps is None)[:, :, 0]
         e = rel_err(got[b], exp)
@@ -205,12 +206,17 @@ def test_caf_multi(n, R, F, nref, method, n_valid, mode):
     """prc_caf_execute_multi: every reference channel, the surveillance channel, the window and each outs[i] guarded
     separately, at frame strides n + 1, n + 4099 and (full frames) the overlapped n / 2 with a Kaiser window, and once
     without a window; outs[i] of the first tight call against the oracle (last frame, last illuminator)"""
+    strides = GAPS + (("overlap",) if n_valid is None else ())      # n_valid < n: frame_stride >= n
+    _caf_multi_check(n, R, F, nref, method, n_valid, mode, [(st, True) for st in strides] + [(1, False)])
+
+
+def _caf_multi_check(n, R, F, nref, method, n_valid, mode, runs, NF=NF):
+    """``runs``: (frame stride mode, windowed) per guarded call; the first one is held to the oracle"""
     valid = n if n_valid is None else n_valid
     kaiser = np.kaiser(n, 5.0)
     plan = engine.CafPlan(n, R, F, NF * nref, method=method, multi=mode)
-    strides = GAPS + (("overlap",) if n_valid is None else ())      # n_valid < n: frame_stride >= n
-    for k, (st, win) in enumerate([(st, kaiser) for st in strides] + [(1, None)]):
-        refs, srv = _caf_data(n, valid, R, st, 7000 + n + R, nref)
+    for k, (st, win) in enumerate([(st, kaiser if w else None) for st, w in runs]):
+        refs, srv = _caf_data(n, valid, R, st, 7000 + n + R, nref, NF)
         ins = {f"ref{i}": _caf_in(refs[i], n, valid, st) for i in range(nref)}
         ins["srv"] = _caf_in(srv, n, valid, st)
         if win is not None:
@@ -235,20 +241,21 @@ FIVE = (0, 1, -1, 2, -2)
 
 
 def _ls_check(plan, n, T, bins, gap, ref, srv, fs=1.0e4, reg=0.0, out_gap=7):
+    nb = ref.shape[0]                                                              # NB, or fewer blocks of a plan made for NB
     ins = {"ref": guard.In(_dev(ref), n + gap), "srv": guard.In(_dev(srv), n + gap)}
-    outs = {"out": guard.Out(NB, n, torch.complex64, n + gap + out_gap),          # an out_stride different from stride
-            "taps": guard.Out(1, NB * T, torch.complex128)}
+    outs = {"out": guard.Out(nb, n, torch.complex64, n + gap + out_gap),          # an out_stride different from stride
+            "taps": guard.Out(1, nb * T, torch.complex128)}
 
     def run(a, s):
-        plan.execute(a["ref"], a["srv"], a["out"], NB, s["ref"], s["out"], fs, bins, reg, a["taps"])
+        plan.execute(a["ref"], a["srv"], a["out"], nb, s["ref"], s["out"], fs, bins, reg, a["taps"])
         _sync()
     got = guard.check(run, ins, outs)
-    return _host(got.tight["out"]), _host(got.tight["taps"]).reshape(NB, T)
+    return _host(got.tight["out"]), _host(got.tight["taps"]).reshape(nb, T)
 
 
-def _ls_scene(n, L, seed):
-    ref, srv = scene.make_scene(n * NB, 1.0e4, min(L, 200), seed)
-    return ref.reshape(NB, n), srv.reshape(NB, n)
+def _ls_scene(n, L, seed, nb=NB):
+    ref, srv = scene.make_scene(n * nb, 1.0e4, min(L, 200), seed)
+    return ref.reshape(nb, n), srv.reshape(nb, n)
 
 
 LS_CASES = [(1, 4000, 16), (2, 40000, 64), (3, 40000, 64), (0, 40000, 64), (4, 40000, 128), (4, 40000, 2100)]
@@ -316,6 +323,10 @@ NS = 5
 def test_nlms(L):
     """prc_nlms_execute with one, two and four wavefronts per stream and the global-workspace kernel: inputs poisoned,
     taps_in and taps_out guarded, the documented zeros outside [filter_len, n - peek) written"""
+    _nlms_check(L)
+
+
+def _nlms_check(L, gaps=GAPS, NS=NS):
     from oracle import c_oracle
     n, T = L + 500, L + 10
     rng = np.random.default_rng(L)
@@ -323,7 +334,7 @@ def test_nlms(L):
     ref = np.stack([a[7 * s:7 * s + n] for s in range(NS)])
     srv = np.stack([b[7 * s:7 * s + n] for s in range(NS)])
     tin = _cplx(rng, NS, T) * np.float32(0.05 / np.sqrt(T))
-    for gap in GAPS:
+    for gap in gaps:
         ins = {"ref": guard.In(_dev(ref), n + gap), "srv": guard.In(_dev(srv), n + gap), "tin": guard.In(_dev(tin))}
         outs = {"out": guard.Out(NS, n, torch.complex64, n + gap + 3), "tout": guard.Out(1, NS * T, torch.complex64)}
 
@@ -340,11 +351,15 @@ def test_nlms(L):
 @pytest.mark.parametrize("D,L", [(64, 8), (1034, 32), (2100, 16)])
 def test_gal(D, L):
     """prc_gal_execute: inputs poisoned, out / k_out / h_out guarded, the workspace holding NaN before the call"""
+    _gal_check(D, L)
+
+
+def _gal_check(D, L, gaps=GAPS, NS=NS):
     from gal_oracle import gal_jpe
     n = 300
     sc = [scene.make_ar2_scene(n, 262144.0, 64, 9000 + D + s) for s in range(NS)]
     ref, srv = np.stack([r[:n] for r, _ in sc]), np.stack([v[:n] for _, v in sc])
-    for gap in GAPS:
+    for gap in gaps:
         ins = {"ref": guard.In(_dev(ref), n + gap), "srv": guard.In(_dev(srv), n + gap)}
         outs = {"out": guard.Out(NS, n, torch.complex64, n + gap + 5), "k": guard.Out(1, NS * D, torch.complex64),
                 "h": guard.Out(1, NS * D, torch.complex64)}

@@ -28,10 +28,12 @@ def scene(wrap):
 
 
 @pytest.mark.parametrize("wrap", [True, False])
-def test_echo_cancel_guard_bands(gpu_ready, wrap):
+def test_echo_cancel_guard_bands(gpu_ready, wrap, NF=NF, STRIDE=STRIDE, OUT_STRIDE=OUT_STRIDE):
+    """``NF``, ``STRIDE``, ``OUT_STRIDE``: tests/test_gpu_far_blocks.py runs the first two frames 4 GiB apart"""
     import torch
     from passiveradar_amd import _lib, engine
     ref, srv, lags, dops = scene(wrap)
+    ref, srv = ref[:NF], srv[:NF]
     rec = np.zeros((NF, M), _lib.ECHO_ATOM_DTYPE)
     rec["lag"], rec["doppler"] = 2 ** 31 - 1, np.nan           # what the slots beyond a count hold: never read
     counts = np.zeros(NF, np.int32)
@@ -64,4 +66,5 @@ def test_echo_cancel_guard_bands(gpu_ready, wrap):
         assert np.abs(out[b] - want).max() <= 2e-6 * np.abs(srv[b]).max()
         assert np.abs(fit[b]["doppler"][:k] - wfit["doppler"]).max(initial=0) <= 1e-6 * FS / N
         assert not fit[b][k:].view(np.uint8).any()
-    assert np.array_equal(out[2].view(np.uint32), srv[2].view(np.uint32))
+    if NF > 2:
+        assert np.array_equal(out[2].view(np.uint32), srv[2].view(np.uint32))

@@ -23,8 +23,8 @@ def dev(a):
 
 @pytest.mark.parametrize("wrap", [True, False])
 @pytest.mark.parametrize("n", [6001, 4096])
-def test_guard_bands_patch(gpu_ready, n, wrap):
-    """a stack of two frames with a gap between them; lag origins at both ends of the allowed range, -(n-1) and n-1, whose
+def test_guard_bands_patch(gpu_ready, n, wrap, gap=1001):
+    """a stack of two frames with a gap between them (``gap``: tests/test_gpu_far_blocks.py passes 4 GiB); lag origins at both ends of the allowed range, -(n-1) and n-1, whose
     16 lags run off either end of the frame; patches on both frames"""
     import torch
     from passiveradar_amd import _lib, engine
@@ -36,7 +36,7 @@ def test_guard_bands_patch(gpu_ready, n, wrap):
     rec = engine.patch_list(lags, dops, frame, 2, n)
     npatches = rec.shape[0]
     st = _lib.torch_stream_ptr()
-    nws = engine.xambg_patch_workspace_bytes(engine.patch_desc(n, nl, nd, fs, step, wrap, 2, n + 1001), npatches)
+    nws = engine.xambg_patch_workspace_bytes(engine.patch_desc(n, nl, nd, fs, step, wrap, 2, n + gap), npatches)
     assert nws % 16 == 0
 
     def run(args, s):
@@ -48,7 +48,7 @@ def test_guard_bands_patch(gpu_ready, n, wrap):
         torch.cuda.synchronize()
 
     got = guard.check(run,
-                      {"ref": guard.In(dev(ref), stride=n + 1001), "srv": guard.In(dev(srv), stride=n + 1001),
+                      {"ref": guard.In(dev(ref), stride=n + gap), "srv": guard.In(dev(srv), stride=n + gap),
                        "window": guard.In(dev(w).reshape(1, -1)),
                        "patches": guard.In(dev(rec.view(np.int64)).reshape(1, -1))},
                       {"out": guard.Out(npatches, nd * nl, torch.complex64),

@@ -253,9 +253,10 @@ def test_addressing_past_2_31_bytes(gpu_ready):
 
 @pytest.mark.parametrize("q", [10, O.TILE_MAX_Q + 1], ids=["tile", "direct"])
 @pytest.mark.parametrize("mix", [0, 1])
-def test_guard_bands_fir_decimate(gpu_ready, q, mix):
+def test_guard_bands_fir_decimate(gpu_ready, q, mix, gap=1001, far_in=0):
     """two int8 channels interleaved sample by sample (step 2, channel stride 1), a tile and a half of outputs: the input is
-    ONE guarded block of both channels, the output two blocks at a stride longer than their extent"""
+    ONE guarded block of both channels, the output two blocks at a stride longer than their extent (``gap``; with ``far_in``
+    the channels are two input blocks of step 1 that many samples apart: tests/test_gpu_far_blocks.py passes 4 GiB)"""
     import torch
     from passiveradar_amd import _lib
     lib = _lib.lib()
@@ -272,11 +273,13 @@ def test_guard_bands_fir_decimate(gpu_ready, q, mix):
     st = _lib.torch_stream_ptr()
 
     def run(a, s):
-        _lib.check(lib.prc_fir_decimate(C.byref(d), taps.data_ptr(), a["x"].data_ptr(), n, 2, 1, 2, a["out"].data_ptr(), 1,
+        step, stride = (1, s["x"] // 2) if far_in else (2, 1)
+        _lib.check(lib.prc_fir_decimate(C.byref(d), taps.data_ptr(), a["x"].data_ptr(), n, step, stride, 2, a["out"].data_ptr(), 1,
                                         s["out"], st))
         torch.cuda.synchronize()
 
-    got = guard.check(run, {"x": guard.In(dev(both).reshape(1, -1))}, {"out": guard.Out(2, m, torch.complex64, stride=m + 1001)})
+    x = guard.In(dev(np.stack(chans)), 2 * (n + far_in)) if far_in else guard.In(dev(both).reshape(1, -1))
+    got = guard.check(run, {"x": x}, {"out": guard.Out(2, m, torch.complex64, stride=m + gap)})
     out = got.tight["out"].cpu().numpy()
     for c in range(2):
         z = O.tuned(chans[c], fc, fs) if mix else O.deinterleave(chans[c])

@@ -211,13 +211,14 @@ def test_determinism_also_from_four_threads(gpu_ready):
 
 @pytest.mark.parametrize("dtype", ["complex64", "int8"])
 @pytest.mark.parametrize("cross", [False, True], ids=["psd", "csd"])
-def test_guard_bands(gpu_ready, dtype, cross):
+def test_guard_bands(gpu_ready, dtype, cross, nfft=256, gap=1001):
     """prc_welch on guarded x, y, out and workspace: two channels at stride > extent, nfft 256, noverlap 37 and a whole
-    segment's worth of samples minus one after the last segment -- reading 'one more segment' lands in poison"""
+    segment's worth of samples minus one after the last segment -- reading 'one more segment' lands in poison
+    (``nfft``, ``gap``: tests/test_gpu_far_blocks.py runs 64-point segments with the channels 4 GiB apart)"""
     import torch
     from passiveradar_amd import _lib
     lib = _lib.lib()
-    nfft, noverlap, nch, nseg, navg = 256, 37, 2, 6, 2
+    noverlap, nch, nseg, navg = 37, 2, 6, 2
     hop = nfft - noverlap
     n = nfft + (nseg - 1) * hop + hop - 1
     rows = nseg // navg
@@ -236,11 +237,11 @@ def test_guard_bands(gpu_ready, dtype, cross):
         pairs = [P.int8_raw(n, s) for s in (71, 72, 73, 74)]
         xs, ys = np.stack([pairs[0][0], pairs[1][0]]), np.stack([pairs[2][0], pairs[3][0]])      # [2, 2 n] scalars
         zx, zy = [pairs[0][1], pairs[1][1]], [pairs[2][1], pairs[3][1]]
-        per, stride = 2, 2 * n + 2 * 1001
+        per, stride = 2, 2 * n + 2 * gap
     else:
         zx, zy = [P.dc(n, 71), P.white(n, 72)], [P.white(n, 73), P.dc(n, 74)]
         xs, ys = np.stack(zx), np.stack(zy)
-        per, stride = 1, n + 1001
+        per, stride = 1, n + gap
 
     def run(a, s):
         assert s["x"] % per == 0 and (not cross or s["y"] == s["x"])
