@@ -36,7 +36,8 @@
  *     two display entry points, tests/test_gpu_psd.py prc_welch, tests/test_gpu_preproc.py prc_fir_decimate, prc_shift and
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
  *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots, tests/test_gpu_tbd_bounds.py prc_tbd and
- *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel, tests/test_gpu_channelize_bounds.py prc_channelize;
+ *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel, tests/test_gpu_channelize_bounds.py prc_channelize,
+ *     tests/test_gpu_map_fuse_bounds.py prc_fuse;
  *     tests/test_gpu_far_blocks.py holds the strided entry points to it with the blocks more than 4 GiB apart and the dense
  *     stacks with their last frame beyond 2^32 bytes, tests/test_gpu_long_streams.py the whole-recording entry points on
  *     streams past 2^31 samples and 2^32 bytes).  Every length, stride and step declared int64_t either works at any such
@@ -58,7 +59,9 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, seventh edition (additions only, the number stays as for the editions below): prc_channelize_desc, prc_channelize,
+#define PRC_VERSION 680   /* 680, eighth edition (additions only, the number stays as for the editions below): prc_fuse_desc, prc_fuse
+                             (non-coherent fusion of several illuminators' maps on a position-velocity grid, on device);
+                             680, seventh edition (additions only, the number stays as for the editions below): prc_channelize_desc, prc_channelize,
                              PRC_OPT_CHANNELIZE_FORM (uniform polyphase filter bank: K of M channels out of one pass over the raw samples);
                              680, sixth edition (additions only, the number stays as for the editions below): prc_echo_desc, prc_echo_atom, prc_echo_fit,
                              prc_echo_cancel_workspace_bytes, prc_echo_cancel (joint least-squares removal of strong echoes at any lag and Doppler);
@@ -766,6 +769,69 @@ int prc_tbd(const prc_tbd_desc* desc, const float* stat, const int32_t* row_shif
 int prc_tbd_trace(const prc_tbd_desc* desc, const uint8_t* back, const int32_t* row_shift /* or NULL */, int32_t nframes,
                   const int32_t* ends /* [nends][2]: frame, cell */, int32_t nends, int32_t depth, int32_t* paths /* [nends][depth] */,
                   void* stream);
+
+/* Fusion of several illuminators' maps on a position-velocity grid: the third consumer of a stack of
+ * CFAR maps beside prc_plots and prc_tbd, and the first of the K stacks of prc_caf_execute_multi together.
+ * Beyond the reference (which has one illuminator): each illuminator puts a target on an ellipsoid (excess bistatic range) and
+ * on a plane in velocity space (bistatic Doppler); only the true position and velocity lie on all of them.  Every
+ * (x, y, vx, vy) hypothesis is scored by reading the cell each illuminator's map would show it in, the scores are combined
+ * without phase, and per position cell the best velocity is kept.  tests/fuse_oracle.py is this definition in NumPy; the device
+ * result equals it bit for bit.
+ * Layout: stat: DEVICE float32, the map [H][W] (h = Doppler row, w = range column, as prc_cfar2d / prc_cfar_os / prc_tbd) of
+ *   illuminator k, frame f at stat + k illum_stride + f frame_stride (elements); best: DEVICE float32 [nframes][ny][nx]; vel:
+ *   DEVICE int32 [nframes][ny][nx] or NULL; illum_host: HOST double [nillum][PRC_FUSE_ILLUM_DOUBLES], per illuminator
+ *   {tx[3], wavelength, baseline, col0, col_per_m, row0, row_per_hz} -- nine values (baseline = |tx - rx| as the caller
+ *   computed it); it is read before the call returns and travels in the kernel arguments: nothing is queued from caller memory.
+ * Arithmetic: all geometry is float64, every operation rounded on its own (no fused multiply-add), in the order written.
+ * Position: cell (iy, ix) is p = (x0 + ix dx, y0 + iy dy, z).
+ * Per cell and illuminator: d_t = sqrt(((px - tx_x)^2 + (py - tx_y)^2) + (pz - tx_z)^2), d_r the same against rx;
+ *   col = rint(col0 + ((d_t + d_r) - baseline) col_per_m);  g_x = ((px - tx_x) / d_t + (px - rx_x) / d_r) / wavelength, g_y the
+ *   same in y; a quotient whose distance is 0 is 0.  rint rounds halves to even.
+ * Velocity: hypothesis j = jy nvx + jx has v = (vx0 + jx dvx, vy0 + jy dvy), no vertical component;
+ *   f = -(g_x vx + g_y vy) (positive Doppler: the bistatic range is closing, as in prc_tbd's row shifts);
+ *   row = rint(row0 + f row_per_hz).
+ * Sample: s_k = stat_k[row][col] if 0 <= row <= H - 1 and 0 <= col <= W - 1, compared in float64 before any conversion (a NaN
+ *   or a huge value misses); otherwise s_k = 0.0f.
+ * Combine: PRC_FUSE_SUM: S = ((s_0 + s_1) + s_2) ... in float32, each sum rounded; PRC_FUSE_MIN: m = s_0, then
+ *   m = s_k < m ? s_k : m (a NaN s_k, k >= 1, is passed over; a NaN s_0 stays).
+ * Reduce: best = -Inf, vel = -1; over ascending j, hypothesis j is chosen iff S > best (float32 compare): ties go to the lowest
+ *   j, a NaN (or -Inf) is never chosen.  best[f][iy][ix] = the chosen S, vel[f][iy][ix] = the chosen j.  Nothing depends on
+ *   the frame except the samples.
+ * Kernels (form): PRC_FUSE_FORM_GLOBAL gathers the samples from global memory.  PRC_FUSE_FORM_LDS: a workgroup owns a tile of
+ *   8 x 8 (above four illuminators: 4 x 4) neighbouring position cells and a run of frames, computes the geometry once, and -- neighbouring cells see
+ *   neighbouring columns -- stages per frame and illuminator only the band of columns its cells read, [H][cmax_k - cmin_k + 1],
+ *   in LDS and gathers from there, where the K bands fit PRC_FUSE_LDS_BYTES less 2 KiB; a tile whose bands do not fit gathers
+ *   from global memory.  PRC_FUSE_FORM_AUTO (0) = the shipped choice.  Every form writes the same bytes.  In both several lanes
+ *   split a cell's hypotheses and merge their partial results under the rule above (larger S, at equal S the lower j).
+ * The call does not allocate, free, copy or synchronise and can be captured.  No atomics: the bytes out are a pure function of
+ * the arguments.  Element alignment suffices; every index into stat is formed in 64 bits, so the maps may lie anywhere.
+ * PRC_EINVAL (host arithmetic, no device needed): a bad descriptor header; nillum outside 1 .. PRC_FUSE_MAX_ILLUM; H, W, nx, ny,
+ * nvx or nvy < 1; H W, nx ny or nvx nvy > 2^31 - 1; more than 2^22 tiles of 4 x 4 cells; an unknown combine or form; a
+ * non-finite grid, velocity, receiver or illuminator parameter; a wavelength <= 0; nframes < 0; strides that let two maps
+ * overlap (a stride counts only where there is a second illuminator / frame; negative strides are refused); a null
+ * illum_host; a null stat or best with nframes > 0.  nframes == 0 is a no-op. */
+#define PRC_FUSE_MAX_ILLUM 8        /* the reference channels prc_caf_execute_multi takes in one call */
+#define PRC_FUSE_ILLUM_DOUBLES 9
+#define PRC_FUSE_LDS_BYTES 159744   /* 156 KiB of the 160 KiB a CDNA4 workgroup can address */
+typedef enum prc_fuse_combine { PRC_FUSE_SUM = 0, PRC_FUSE_MIN = 1 } prc_fuse_combine;
+typedef enum prc_fuse_form { PRC_FUSE_FORM_AUTO = 0, PRC_FUSE_FORM_GLOBAL = 1, PRC_FUSE_FORM_LDS = 2 } prc_fuse_form;
+typedef struct prc_fuse_desc {
+    uint32_t struct_size;  /* sizeof(prc_fuse_desc) as the host compiled it (see Conventions)                   */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                                    */
+    int32_t nillum;        /* K illuminators, 1 .. PRC_FUSE_MAX_ILLUM                                           */
+    int32_t H, W;          /* Doppler rows, range columns of a map (>= 1 each)                                  */
+    int32_t nx, ny;        /* position cells                                                                    */
+    int32_t nvx, nvy;      /* velocity hypotheses                                                               */
+    int32_t combine;       /* prc_fuse_combine                                                                  */
+    int32_t form;          /* prc_fuse_form                                                                     */
+    int32_t reserved;      /* 0                                                                                 */
+    double x0, dx, y0, dy, z;          /* position of cell (iy, ix): (x0 + ix dx, y0 + iy dy, z), metres        */
+    double vx0, dvx, vy0, dvy;         /* velocity of hypothesis (jy, jx): (vx0 + jx dvx, vy0 + jy dvy), m/s    */
+    double rx[3];                      /* the receiver, metres                                                  */
+} prc_fuse_desc;
+#define PRC_FUSE_DESC_SIZE_MIN 144u
+int prc_fuse(const prc_fuse_desc* desc, const double* illum_host, const float* stat, int64_t illum_stride, int64_t frame_stride,
+             int32_t nframes, float* best /* [nframes][ny][nx] */, int32_t* vel /* or NULL */, void* stream);
 
 /* ---- single-target tracker: target_detection.py:530-681 (simple_target_tracker) ------------------------------------ */
 /* Frames are [nframes][H][W] (H Doppler rows, W range columns), float32 (the CFAR output) or float64.  The result is the

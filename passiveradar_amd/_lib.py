@@ -187,6 +187,22 @@ TBD_FRAMES, TBD_FRAMES_MAX = 8, 32      # PRC_TBD_FRAMES, PRC_TBD_FRAMES_MAX: fr
 TBD_LDS_BYTES = 159744                  # PRC_TBD_LDS_BYTES
 TBD_NONE = 255                          # the back pointer of a cell without a predecessor
 
+
+class FuseDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("nillum", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("nvx", C.c_int32), ("nvy", C.c_int32), ("combine", C.c_int32), ("form", C.c_int32), ("reserved", C.c_int32),
+                ("x0", C.c_double), ("dx", C.c_double), ("y0", C.c_double), ("dy", C.c_double), ("z", C.c_double),
+                ("vx0", C.c_double), ("dvx", C.c_double), ("vy0", C.c_double), ("dvy", C.c_double), ("rx", C.c_double * 3)]
+
+
+FUSE_MAX_ILLUM, FUSE_ILLUM_DOUBLES = 8, 9      # PRC_FUSE_MAX_ILLUM, PRC_FUSE_ILLUM_DOUBLES
+FUSE_LDS_BYTES = 159744                        # PRC_FUSE_LDS_BYTES
+FUSE_SUM, FUSE_MIN = 0, 1                      # prc_fuse_combine
+FUSE_COMBINES = {"sum": FUSE_SUM, "min": FUSE_MIN}
+FUSE_FORM_AUTO, FUSE_FORM_GLOBAL, FUSE_FORM_LDS = 0, 1, 2      # prc_fuse_form
+
+
 class EchoDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
                 ("n", C.c_int64), ("frame_stride", C.c_int64), ("out_stride", C.c_int64), ("nframes", C.c_int32),
@@ -318,6 +334,8 @@ _SIGNATURES = {
     "prc_tbd": (C.c_int, [C.POINTER(TbdDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_tbd_trace": (C.c_int, [C.POINTER(TbdDesc), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_void_p]),
+    "prc_fuse": (C.c_int, [C.POINTER(FuseDesc), C.POINTER(C.c_double), C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                           C.c_void_p, C.c_void_p]),
     "prc_strack_workspace_bytes": (C.c_int, [C.POINTER(StrackDesc), C.c_int32, C.POINTER(C.c_size_t)]),
     "prc_strack_run": (C.c_int, [C.POINTER(StrackDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),

@@ -530,6 +530,31 @@ def tbd_trace(desc, back, row_shift, nframes, ends, nends, depth, paths, stream=
                               _ptr(paths), stream))
 
 
+def fuse_desc(nillum, H, W, grid, velocities, rx, z=0.0, combine=_lib.FUSE_SUM, form=None):
+    """prc_fuse_desc of include/prcore.h: ``grid`` = (x0, dx, nx, y0, dy, ny), ``velocities`` = (vx0, dvx, nvx, vy0, dvy, nvy),
+    ``rx`` the receiver's three coordinates; form None: the shipped choice"""
+    d = _lib.FuseDesc()
+    d.nillum, d.H, d.W = int(nillum), int(H), int(W)
+    d.x0, d.dx, d.nx, d.y0, d.dy, d.ny = float(grid[0]), float(grid[1]), int(grid[2]), float(grid[3]), float(grid[4]), int(grid[5])
+    d.vx0, d.dvx, d.nvx = float(velocities[0]), float(velocities[1]), int(velocities[2])
+    d.vy0, d.dvy, d.nvy = float(velocities[3]), float(velocities[4]), int(velocities[5])
+    d.z, d.combine, d.form = float(z), int(combine), _lib.FUSE_FORM_AUTO if form is None else int(form)
+    d.rx[0], d.rx[1], d.rx[2] = (float(v) for v in rx)
+    return d
+
+
+def fuse_execute(desc, illum, stat, illum_stride, frame_stride, nframes, best, vel, stream=None):
+    """prc_fuse: ``illum`` is a host float64 array [nillum, 9] (None only passes the null pointer on); ``stat``, ``best`` and
+    ``vel`` are device buffers or torch tensors (``vel`` may be None); the strides are in elements"""
+    if illum is not None:
+        illum = np.ascontiguousarray(illum, dtype=np.float64)
+        ip = illum.ctypes.data_as(C.POINTER(C.c_double))
+    else:
+        ip = None
+    check(lib().prc_fuse(C.byref(desc), ip, _ptr(stat), int(illum_stride), int(frame_stride), int(nframes), _ptr(best), _ptr(vel),
+                         stream))
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

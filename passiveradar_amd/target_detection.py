@@ -7,7 +7,9 @@ chain (:46-61).  Beyond the reference: ``CFAR_2D_OS``, the order-statistic CFAR 
 ``cfar_training_cells`` and ``os_cfar_threshold``), which the chains take with ``cfar="os"``, ``refine_peaks``, and
 ``extract_plots``, the plot extractor between a CFAR map and the tracker (``track_maps(..., measure="plots")``), and
 track-before-detect: ``track_before_detect`` (the Viterbi integration of a stack of CFAR maps along the paths the Doppler
-rows allow, ``tbd_row_shifts``), ``tbd_paths`` and the chain ``tbd_maps``."""
+rows allow, ``tbd_row_shifts``), ``tbd_paths`` and the chain ``tbd_maps``; and the fusion of several illuminators' maps on
+a position-velocity grid: ``fuse_maps`` (with ``bistatic_axes`` and the forward model ``bistatic_cell``) and the chain
+``locate_maps``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +23,7 @@ __all__ = ["CFAR_2D", "CFAR_2D_abs", "CFAR_2D_OS", "cfar_training_cells", "os_cf
            "multitarget_tracker", "track_maps",
            "kalman_filter_dtype", "target_track_dtype", "simple_target_tracker", "simple_track_maps",
            "target_track_dtype_simple", "refine_peaks", "extract_plots", "tbd_row_shifts", "track_before_detect", "tbd_paths",
-           "tbd_maps"]
+           "tbd_maps", "bistatic_axes", "bistatic_cell", "fuse_maps", "locate_maps"]
 
 
 def _map_dtype(cplx):
@@ -680,6 +682,175 @@ def tbd_maps(xambg, frame_extent, frame_interval, wavelength, *, thresh, depth=1
     paths = tbd_paths(back, ends.reshape(N * cap, 2), depth, kw["row_shifts"], doppler_reach=kw.get("doppler_reach", 1),
                       range_reach=kw.get("range_reach", 1))
     return counts, meas, index, paths.reshape(N, cap, int(depth))
+
+
+# ---- fusion of several illuminators' maps on a position-velocity grid (beyond the reference) --------
+SPEED_OF_LIGHT = 299792458.0
+
+
+def bistatic_axes(rangeBins, freqBins, n, sampleRate):
+    """``(col0, col_per_m, row0, row_per_hz)`` of a fast_xambg surface: an echo with ``r`` metres of excess bistatic range and
+    ``f`` Hz of Doppler lands in column ``col0 + r col_per_m`` and row ``row0 + f row_per_hz``.  col = R - lag and
+    row = F/2 - f CPI (the inverse of scene.expected_peak_cell): col0 = R, col_per_m = -fs/c, row0 = F/2, row_per_hz = -n/fs."""
+    fs = float(sampleRate)
+    return float(rangeBins), -fs / SPEED_OF_LIGHT, float(freqBins) / 2.0, -float(n) / fs
+
+
+def _fuse_baseline(tx, rx):
+    """|tx - rx| in float64, summed as prc_fuse sums a distance"""
+    a = [np.float64(tx[i]) - np.float64(rx[i]) for i in range(3)]
+    return float(np.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]))
+
+
+def bistatic_cell(position, velocity, tx, rx, wavelength, axes):
+    """The forward model of prc_fuse in float64, operation for operation: the ``(row, col)`` (integers, not clipped to the
+    map) in which an echo of a target at ``position`` (x, y, z) moving at ``velocity`` (vx, vy; no vertical component) lands
+    on the surface of the illuminator at ``tx`` seen from ``rx``, ``axes`` = (col0, col_per_m, row0, row_per_hz)."""
+    f8 = np.float64
+    p, t, r = [f8(v) for v in position], [f8(v) for v in tx], [f8(v) for v in rx]
+    vx, vy, lam = f8(velocity[0]), f8(velocity[1]), f8(wavelength)
+    col0, col_per_m, row0, row_per_hz = (f8(v) for v in axes)
+    at, ar = [p[i] - t[i] for i in range(3)], [p[i] - r[i] for i in range(3)]
+    dt = np.sqrt((at[0] * at[0] + at[1] * at[1]) + at[2] * at[2])
+    dr = np.sqrt((ar[0] * ar[0] + ar[1] * ar[1]) + ar[2] * ar[2])
+    col = np.rint(col0 + ((dt + dr) - f8(_fuse_baseline(tx, rx))) * col_per_m)
+
+    def quot(a, d):
+        return f8(0.0) if d == 0.0 else a / d
+
+    gx = (quot(at[0], dt) + quot(ar[0], dr)) / lam
+    gy = (quot(at[1], dt) + quot(ar[1], dr)) / lam
+    f = -(gx * vx + gy * vy)
+    return int(np.rint(row0 + f * row_per_hz)), int(col)
+
+
+def _fuse_illum(illuminators, rx):
+    """the host array [K, 9] of prc_fuse from ``(tx, wavelength, axes)`` triples: the baseline is computed here"""
+    rows = []
+    for tx, wavelength, axes in illuminators:
+        if len(tx) != 3 or len(axes) != 4:
+            raise ValueError("an illuminator is (tx[3], wavelength, (col0, col_per_m, row0, row_per_hz))")
+        rows.append([float(tx[0]), float(tx[1]), float(tx[2]), float(wavelength), _fuse_baseline(tx, rx)] + [float(v) for v in axes])
+    return np.array(rows, dtype=np.float64).reshape(len(rows), _lib.FUSE_ILLUM_DOUBLES)
+
+
+def _fuse_strides_ok(HW, K, s_illum, nframes, s_frame):
+    """prc_fuse's condition on the two strides: no two of the K x nframes maps overlap"""
+    if (K > 1 and s_illum < HW) or (nframes > 1 and s_frame < HW):
+        return False
+    if K == 1 or nframes == 1:
+        return True
+    return s_illum >= s_frame * (nframes - 1) + HW or s_frame >= s_illum * (K - 1) + HW
+
+
+def fuse_maps(stat, illuminators, rx, grid, velocities, z=0.0, combine="sum", form=None, return_vel=True):
+    """Non-coherent fusion of K illuminators' maps on a position-velocity grid (prc_fuse of include/prcore.h): per position
+    cell (iy, ix) at (x0 + ix dx, y0 + iy dy, z) and velocity hypothesis j = jy nvx + jx at (vx0 + jx dvx, vy0 + jy dvy) the
+    cell each illuminator's map would show that target in is read, the K samples are added (``combine="sum"``) or their
+    minimum is taken (``"min"``), and per position cell the best score over the hypotheses and its j are kept.
+    ``stat`` is [K, nframes, H, W] (or a list of K stacks [nframes, H, W]), float32 CFAR maps or any statistic, NumPy or a
+    torch device tensor; ``illuminators`` a sequence of K ``(tx, wavelength, axes)`` with ``axes`` as bistatic_axes returns
+    them; ``rx`` the receiver; ``grid`` = (x0, dx, nx, y0, dy, ny); ``velocities`` = (vx0, dvx, nvx, vy0, dvy, nvy).
+    Returns ``(best, vel)``, float32 and int32 [nframes, ny, nx] (vel None with ``return_vel=False``): arrays for NumPy, tensors
+    on the caller's device and torch's current stream for torch.  A device tensor whose maps are dense and do not overlap is
+    read in place through its two leading strides, whatever they are; any other is copied first.  ``form``: None = the
+    shipped kernel choice, 1 = gathers from global memory, 2 = gathers from LDS where a tile's columns fit."""
+    if combine not in _lib.FUSE_COMBINES:
+        raise ValueError(f"combine is 'sum' or 'min', not {combine!r}")
+    if isinstance(stat, (list, tuple)):
+        side = residence.of(stat[0], *stat[1:], pooled=False, mixed="the stacks are all NumPy arrays or all device tensors")
+        if side.torch:
+            import torch
+            stat = torch.stack([s.to(torch.float32) for s in stat])
+        else:
+            stat = np.stack([np.asarray(s, dtype=np.float32) for s in stat])
+    else:
+        side = residence.of(stat, pooled=False)
+    shape = residence.shape(stat)
+    if len(shape) != 4:
+        raise ValueError("fuse_maps takes [K, nframes, H, W] maps or a list of K stacks [nframes, H, W]")
+    K, nframes, H, W = (int(v) for v in shape)
+    if K != len(illuminators):
+        raise ValueError(f"{K} stacks of maps, {len(illuminators)} illuminators")
+    if len(rx) != 3 or len(grid) != 6 or len(velocities) != 6:
+        raise ValueError("rx is (x, y, z), grid (x0, dx, nx, y0, dy, ny), velocities (vx0, dvx, nvx, vy0, dvy, nvy)")
+    desc = engine.fuse_desc(K, H, W, grid, velocities, rx, z, _lib.FUSE_COMBINES[combine], form)
+    illum = _fuse_illum(illuminators, rx)
+    s_illum, s_frame = max(nframes, 1) * H * W, H * W
+    if side.torch and residence.dtype_name(stat) == "float32" and stat.numel():
+        st = stat.stride()
+        if st[3] == 1 and st[2] == W and _fuse_strides_ok(H * W, K, st[0], nframes, st[1]):
+            s_illum, s_frame = int(st[0]), int(st[1])
+        else:
+            stat = stat.contiguous()
+    # every argument check of prc_fuse, on the host (ValueError), before a device is touched
+    engine.fuse_execute(desc, illum, None, s_illum, s_frame, 0, None, None)
+    oshape = (nframes, desc.ny, desc.nx)
+    if nframes == 0:
+        return side.nothing(oshape, np.float32), (side.nothing(oshape, np.int32) if return_vel else None)
+    if side.torch and residence.dtype_name(stat) == "float32":
+        x = residence._TorchBuf(stat)              # in place: the strides say where the maps are
+    else:
+        x = side.put("stat", stat, np.float32)
+    best = side.empty("best", oshape, np.float32)
+    vel = side.empty("vel", oshape, np.int32) if return_vel else None
+    with side.device():
+        engine.fuse_execute(desc, illum, x, s_illum, s_frame, nframes, best, vel, side.stream)
+    return side.result(best, oshape, np.float32), (side.result(vel, oshape, np.int32) if return_vel else None)
+
+
+def locate_maps(xambg_list, illuminators, rx, grid, velocities, z=0.0, *, thresh, npeaks, fw=18, gw=4, cfar="os", cfar_rank=None,
+                combine="sum", form=None):
+    """CFAR each illuminator's stack -> fuse_maps -> the ``npeaks`` strongest cells of ``best`` per frame above ``thresh``:
+    where the targets of a multi-illuminator frame are and how they move.  ``xambg_list`` holds one stack per illuminator as
+    the chains take them (a torch device tensor [N, H, W] or NumPy (H, W, Nframes), complex surfaces or magnitudes); the CFAR
+    is CFAR_2D_OS on the ``plain`` scale (``cfar="os"``) or CFAR_2D / CFAR_2D_abs (``"mean"``); the other arguments are
+    fuse_maps'.  Returns ``(position, velocity, score)``: float64 [N, npeaks, 2] (x, y), float64 [N, npeaks, 2] (vx, vy) and
+    float32 [N, npeaks], strongest first; a slot whose cell is not above ``thresh`` (or that the grid has no cell for) holds
+    NaN, NaN and -Inf.  Arrays for NumPy, tensors on the caller's device for torch (the peaks are picked by torch.topk there)."""
+    _check_cfar(cfar)
+    npeaks, thresh = int(npeaks), float(thresh)
+    if npeaks < 1:
+        raise ValueError(f"npeaks = {npeaks}, not >= 1")
+    if len(xambg_list) != len(illuminators):
+        raise ValueError(f"{len(xambg_list)} stacks of maps, {len(illuminators)} illuminators")
+    maps = []
+    for xambg in xambg_list:
+        side, x, cplx = _maps_stack(xambg, "locate_maps")
+        if cfar == "os":
+            cf = CFAR_2D_OS(x, fw, gw, rank=cfar_rank, scale="plain")
+        else:
+            cf = CFAR_2D_abs(x, fw, gw) if cplx else CFAR_2D(x, fw, gw)
+        maps.append(cf)
+    best, vel = fuse_maps(maps, illuminators, rx, grid, velocities, z, combine, form)
+    x0, dx, nx, y0, dy, ny = float(grid[0]), float(grid[1]), int(grid[2]), float(grid[3]), float(grid[4]), int(grid[5])
+    vx0, dvx, nvx, vy0, dvy = float(velocities[0]), float(velocities[1]), int(velocities[2]), float(velocities[3]), float(velocities[4])
+    N, k = int(best.shape[0]), min(npeaks, nx * ny)
+    if side.torch:
+        import torch
+        score, cell = torch.topk(best.reshape(N, nx * ny), k, dim=1)
+        j = torch.gather(vel.reshape(N, nx * ny), 1, cell).to(torch.int64)
+        pad, stack, where, f8 = (lambda t, v: torch.nn.functional.pad(t, (0, npeaks - k), value=v)), torch.stack, torch.where, torch.float64
+        cell, j, score = pad(cell, 0), pad(j, 0), pad(score, float("-inf"))
+        iy, ix, jy, jx = cell // nx, cell % nx, j // nvx, j % nvx
+        ok = score > thresh
+        nan = torch.full_like(score, float("nan"), dtype=f8)
+        ninf = torch.full_like(score, float("-inf"))
+        ix, iy, jx, jy = ix.to(f8), iy.to(f8), jx.to(f8), jy.to(f8)
+    else:
+        flat = best.reshape(N, nx * ny)
+        order = np.argsort(-np.where(np.isnan(flat), -np.inf, flat), axis=1, kind="stable")[:, :k]
+        score = np.take_along_axis(flat, order, axis=1)
+        j = np.take_along_axis(vel.reshape(N, nx * ny), order, axis=1).astype(np.int64)
+        pad, stack, where, f8 = (lambda t, v: np.pad(t, ((0, 0), (0, npeaks - k)), constant_values=v)), np.stack, np.where, np.float64
+        cell, j, score = pad(order, 0), pad(j, 0), pad(score, -np.inf)
+        iy, ix, jy, jx = cell // nx, cell % nx, j // nvx, j % nvx
+        ok = score > thresh
+        nan = np.full(score.shape, np.nan)
+        ninf = np.full(score.shape, -np.inf, dtype=np.float32)
+    position = stack((where(ok, x0 + ix * dx, nan), where(ok, y0 + iy * dy, nan)), 2)
+    velocity = stack((where(ok, vx0 + jx * dvx, nan), where(ok, vy0 + jy * dvy, nan)), 2)
+    return position, velocity, where(ok, score, ninf)
 
 
 # ---- single-target tracker (target_detection.py:530-681) ---------------------------------------------------------------
