@@ -37,7 +37,7 @@
  *     prc_normalize, tests/test_gpu_patch_bounds.py prc_xambg_patch and prc_xambg_patch_peaks,
  *     tests/test_gpu_cfar_os_bounds.py prc_cfar_os, tests/test_gpu_plots_bounds.py prc_plots, tests/test_gpu_tbd_bounds.py prc_tbd and
  *     prc_tbd_trace, tests/test_gpu_echo_bounds.py prc_echo_cancel, tests/test_gpu_channelize_bounds.py prc_channelize,
- *     tests/test_gpu_map_fuse_bounds.py prc_fuse;
+ *     tests/test_gpu_map_fuse_bounds.py prc_fuse, tests/test_gpu_recip_xambg_bounds.py prc_batch_xambg and prc_ofdm_timing;
  *     tests/test_gpu_far_blocks.py holds the strided entry points to it with the blocks more than 4 GiB apart and the dense
  *     stacks with their last frame beyond 2^32 bytes, tests/test_gpu_long_streams.py the whole-recording entry points on
  *     streams past 2^31 samples and 2^32 bytes).  Every length, stride and step declared int64_t either works at any such
@@ -59,7 +59,10 @@ extern "C" {
 /* zero a descriptor and fill in its header; then set the fields */
 #define PRC_DESC_INIT(d) do { memset(&(d), 0, sizeof(d)); (d).struct_size = (uint32_t)sizeof(d); (d).magic = PRC_DESC_MAGIC; } while (0)
 
-#define PRC_VERSION 680   /* 680, eighth edition (additions only, the number stays as for the editions below): prc_fuse_desc, prc_fuse
+#define PRC_VERSION 680   /* 680, ninth edition (additions only, the number stays as for the editions below): prc_batch_xambg_desc,
+                             prc_batch_xambg_workspace_bytes, prc_batch_xambg, prc_ofdm_timing (reciprocal-filter range-Doppler maps for OFDM
+                             illuminators by the batches algorithm, and the symbol timing that aligns the batches);
+                             680, eighth edition (additions only, the number stays as for the editions below): prc_fuse_desc, prc_fuse
                              (non-coherent fusion of several illuminators' maps on a position-velocity grid, on device);
                              680, seventh edition (additions only, the number stays as for the editions below): prc_channelize_desc, prc_channelize,
                              PRC_OPT_CHANNELIZE_FORM (uniform polyphase filter bank: K of M channels out of one pass over the raw samples);
@@ -261,6 +264,69 @@ int prc_caf_execute_segments(prc_caf_plan* plan, const void* ref, const void* sr
                              int64_t frame_stride, int64_t n_valid, const float* window,
                              int32_t nframes, void* stream);
 int prc_caf_execute_doppler(prc_caf_plan* plan, void* out, int32_t nframes, void* stream);
+
+/* cross-ambiguity surface, batches algorithm with a matched or a RECIPROCAL filter, for OFDM illuminators.
+ * Beyond the reference: on a QAM-OFDM illuminator (DVB-T/T2, DAB, LTE, 5G) the matched filter of fast_xambg lifts the whole
+ * surface by about 1 / sqrt(B T) of every strong echo's peak; dividing each batch of the surveillance channel by the reference
+ * batch's spectrum instead of multiplying by its conjugate turns every echo into a clean impulse per batch, so no data-dependent
+ * pedestal is left.  tests/batch_xambg_oracle.py is this definition in float64.
+ * Per frame: ref, srv complex64 [n]; batch j = 0 .. freq_bins - 1 is the batch_len samples from start + j hop of both channels
+ *   (start >= 0, hop >= 1, start + (freq_bins - 1) hop + batch_len <= n: no wrap, no zero padding; hop < batch_len overlaps).
+ * Per batch: Rj = DFT(r_j), Sj = DFT(s_j), unnormalised, L = batch_len points; P_j = sum_t |r_j[t]|^2;
+ *   G_j(f) = 1 (PRC_BATCH_MATCHED) or 1 / max(|Rj(f)|^2, floor^2 P_j) (PRC_BATCH_RECIPROCAL; 0 where that maximum is 0: a silent
+ *   reference batch contributes nothing.  The clamp is continuous: no threshold at which two roundings could disagree);
+ *   c_j(d) = (1 / L) sum_f G_j(f) Rj(f) conj(Sj(f)) e^{-2 pi i f d / L}, d = 0 .. range_bins < L: circular within the batch, in
+ *   fast_xambg's conjugation convention.
+ * Surface: y[j][k] = window[j] c_j(range_bins - k) (window: DEVICE float32 [freq_bins] or NULL = ones);
+ *   out = fftshift over rows of DFT over j of y: complex64 [nframes][freq_bins][range_bins + 1], C order -- fast_xambg's layout:
+ *   column k is delay range_bins - k, rows mirrored and fftshift-ed, a CPI of freq_bins hop samples.
+ * With the reciprocal filter and batches aligned to the useful parts of the symbols (start = symbol start + cp, hop = nfft + cp,
+ * batch_len = nfft) an echo a ref(t - d), d <= cp, peaks at a freq_bins (occupied carriers / batch_len).  On constant-modulus
+ * carriers (QPSK) the two filters coincide up to scale; with batches that are not aligned the reciprocal filter gains nothing.
+ * Kernels: batch_len 1024 = one wavefront per batch, 4096 = a team of four wavefronts per batch: both channels of a batch are
+ *   loaded once, two forward transforms, the pointwise step in the transforms' permuted frequency layout, ONE inverse transform,
+ *   lags 0 .. range_bins stored into `workspace` in the tile-major layout of the column Doppler kernel, which then runs.  Other
+ *   batch_len, and freq_bins outside 256, 512, 1024, 2048, 4096: PRC_EUNSUPPORTED.
+ * workspace: DEVICE, prc_batch_xambg_workspace_bytes bytes, the caller's; its contents before the call do not matter.
+ * The call does not allocate (the small per-device twiddle tables are made the first time a shape needs them), free, copy or
+ * synchronise, uses no atomics and can be captured on one stream.  Element alignment suffices.  Frame b reads ref and srv only
+ * inside [b frame_stride + start, b frame_stride + start + (freq_bins - 1) hop + batch_len); frame_stride is a 64-bit element
+ * count without a limit.
+ * PRC_EINVAL: a bad descriptor header, an unknown filter, a floor that is negative or not finite (reciprocal filter), nframes < 0,
+ * a null or misaligned pointer.  PRC_ESHAPE (the message names the value and the limit; checked before anything runs):
+ * start < 0; hop < 1; range_bins outside 0 .. batch_len - 1; n outside 1 .. PRC_CAF_MAX_N; a last batch that ends beyond n;
+ * nframes freq_bins > PRC_BATCH_XAMBG_MAX_BATCHES.  nframes == 0 is a no-op. */
+typedef enum prc_batch_filter { PRC_BATCH_MATCHED = 0, PRC_BATCH_RECIPROCAL = 1 } prc_batch_filter;
+/* (struct tag first, typedef after: tests/test_abi.py lists by name the ctypes mirror of every `typedef struct {` with int64_t
+ * fields; tests/test_batch_xambg_host.py holds this one's three to c_int64, and every offset to the layout below) */
+struct prc_batch_xambg_desc {
+    uint32_t struct_size;  /* sizeof(prc_batch_xambg_desc) as the host compiled it (see Conventions)           */
+    uint32_t magic;        /* PRC_DESC_MAGIC                                                                   */
+    int64_t n;             /* samples per frame                                                                */
+    int64_t start;         /* first sample of batch 0                                                          */
+    int64_t hop;           /* samples between batch starts                                                     */
+    int32_t batch_len;     /* L: 1024 or 4096                                                                  */
+    int32_t range_bins;    /* the surface has range_bins + 1 columns                                           */
+    int32_t freq_bins;     /* batches = Doppler rows: 256, 512, 1024, 2048 or 4096                             */
+    int32_t filter;        /* prc_batch_filter                                                                 */
+    float floor;           /* reciprocal filter: |Rj(f)|^2 is held above floor^2 P_j (0.1 is a good start)     */
+    int32_t reserved;      /* 0                                                                                */
+};
+typedef struct prc_batch_xambg_desc prc_batch_xambg_desc;
+#define PRC_BATCH_XAMBG_DESC_SIZE_MIN 56u
+#define PRC_BATCH_XAMBG_MAX_BATCHES ((int64_t)2147483647)   /* nframes * freq_bins of one call */
+int prc_batch_xambg_workspace_bytes(const prc_batch_xambg_desc* desc, int32_t nframes, size_t* bytes);
+int prc_batch_xambg(const prc_batch_xambg_desc* desc, const void* ref, const void* srv, int64_t frame_stride, const float* window,
+                    void* out, int32_t nframes, void* workspace, void* stream);
+/* OFDM symbol timing from the cyclic prefix: for o = 0 .. nfft + cp - 1
+ *   metric[o] = | sum_{s < nsym} sum_{t < cp} ref[o + s (nfft + cp) + t] conj(ref[o + s (nfft + cp) + t + nfft]) |,
+ * the products of the float32 samples summed in float64 (every product is exact there, so the result does not depend on the order
+ * of the sums beyond the last bits); *start_out = the lowest o of the largest metric.  The batches of prc_batch_xambg are aligned
+ * with start = *start_out + cp, hop = nfft + cp, batch_len = nfft.  metric_out: DEVICE float64 [nfft + cp]; start_out: DEVICE int32.
+ * Any nfft >= 2, 1 <= cp < nfft, nsym >= 1 (else PRC_EINVAL); (nsym + 1) (nfft + cp) + nfft <= n and nfft + cp <= 2^31 - 1, else
+ * PRC_ESHAPE (the message names the sizes).  Two launches on `stream`, no allocation, no atomics; capturable. */
+int prc_ofdm_timing(const void* ref, int64_t n, int32_t nfft, int32_t cp, int32_t nsym, double* metric_out, int32_t* start_out,
+                    void* stream);
 
 /* ---- block least-squares clutter cancellers (clutter_removal.py) ------------------- */
 typedef struct prc_ls_desc {

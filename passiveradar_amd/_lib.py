@@ -203,6 +203,19 @@ FUSE_COMBINES = {"sum": FUSE_SUM, "min": FUSE_MIN}
 FUSE_FORM_AUTO, FUSE_FORM_GLOBAL, FUSE_FORM_LDS = 0, 1, 2      # prc_fuse_form
 
 
+class BatchXambgDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
+                ("n", C.c_int64), ("start", C.c_int64), ("hop", C.c_int64), ("batch_len", C.c_int32), ("range_bins", C.c_int32),
+                ("freq_bins", C.c_int32), ("filter", C.c_int32), ("floor", C.c_float), ("reserved", C.c_int32)]
+
+
+BATCH_MATCHED, BATCH_RECIPROCAL = 0, 1                     # prc_batch_filter
+BATCH_FILTERS = {"matched": BATCH_MATCHED, "reciprocal": BATCH_RECIPROCAL}
+BATCH_LENGTHS = (1024, 4096)                               # batch_len prc_batch_xambg transforms
+BATCH_FREQ_BINS = (256, 512, 1024, 2048, 4096)             # freq_bins the column Doppler kernel takes
+BATCH_XAMBG_MAX_BATCHES = 2 ** 31 - 1                      # PRC_BATCH_XAMBG_MAX_BATCHES
+
+
 class EchoDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32),
                 ("n", C.c_int64), ("frame_stride", C.c_int64), ("out_stride", C.c_int64), ("nframes", C.c_int32),
@@ -272,6 +285,10 @@ _SIGNATURES = {
     "prc_caf_execute_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_int32, C.c_void_p]),
     "prc_caf_execute_doppler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "prc_batch_xambg_workspace_bytes": (C.c_int, [C.POINTER(BatchXambgDesc), C.c_int32, C.POINTER(C.c_size_t)]),
+    "prc_batch_xambg": (C.c_int, [C.POINTER(BatchXambgDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                  C.c_void_p, C.c_void_p]),
+    "prc_ofdm_timing": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "prc_ls_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(LsDesc)]),
     "prc_ls_plan_destroy": (C.c_int, [C.c_void_p]),
     "prc_ls_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,

@@ -555,6 +555,33 @@ def fuse_execute(desc, illum, stat, illum_stride, frame_stride, nframes, best, v
                          stream))
 
 
+def batch_xambg_desc(n, batch_len, range_bins, freq_bins, hop=None, start=0, filter=_lib.BATCH_RECIPROCAL, floor=0.1):
+    """prc_batch_xambg_desc of include/prcore.h (hop None: batch_len, batches end to end)"""
+    d = _lib.BatchXambgDesc()
+    d.n, d.start, d.hop = int(n), int(start), int(batch_len if hop is None else hop)
+    d.batch_len, d.range_bins, d.freq_bins = int(batch_len), int(range_bins), int(freq_bins)
+    d.filter, d.floor = int(filter), float(floor)
+    return d
+
+
+def batch_xambg_workspace_bytes(desc, nframes):
+    """device bytes prc_batch_xambg needs in ``workspace`` (its slow-time buffer); validates the descriptor on the host"""
+    nb = C.c_size_t(0)
+    check(lib().prc_batch_xambg_workspace_bytes(C.byref(desc), int(nframes), C.byref(nb)))
+    return int(nb.value)
+
+
+def batch_xambg_execute(desc, ref, srv, frame_stride, window, out, nframes, workspace, stream=None):
+    """batches-algorithm surfaces of ``nframes`` frames (device buffers or torch tensors; ``window`` may be None)"""
+    check(lib().prc_batch_xambg(C.byref(desc), _ptr(ref), _ptr(srv), int(frame_stride), _ptr(window), _ptr(out), int(nframes),
+                                _ptr(workspace), stream))
+
+
+def ofdm_timing(ref, n, nfft, cp, nsym, metric, start, stream=None):
+    """prc_ofdm_timing: the cyclic-prefix metric (device float64 [nfft + cp]) and its argmax (device int32) of ``ref``"""
+    check(lib().prc_ofdm_timing(_ptr(ref), int(n), int(nfft), int(cp), int(nsym), _ptr(metric), _ptr(start), stream))
+
+
 # ---- per-thread plan cache (dask-style concurrent callers each get their own plans) ------
 _tls = threading.local()
 

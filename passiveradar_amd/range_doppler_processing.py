@@ -11,10 +11,10 @@ import functools
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, engine, residence
 
 __all__ = ["fast_xambg", "fast_xambg_multi", "direct_xambg", "caf_plan_for", "set_default_methods", "xambg_patch",
-           "patch_origins", "clean_xambg"]
+           "patch_origins", "clean_xambg", "batch_xambg", "ofdm_symbol_start"]
 
 # Kernel selection used by fast_xambg (0 = let the plan decide).  Not part of the reference
 # signature; tests flip it to run the same cases through every kernel family.
@@ -395,3 +395,101 @@ def clean_xambg(ref, srv, sampleRate, rangeBins, freqBins, *, npeaks=4, doppler_
     rec = np.zeros(lags.shape[0], ECHO_RECORD_DTYPE)
     rec["lag"], rec["doppler"], rec["amplitude"] = lags, f, amp
     return fast_xambg(ref, cleaned, R, F), rec
+
+
+def batch_xambg(refChannel, srvChannel, rangeBins, freqBins, batchLen, *, hop=None, start=0, filter="reciprocal", floor=0.1,
+                window=None):
+    """Range-Doppler map by the batches algorithm with a matched or a RECIPROCAL filter, for QAM-OFDM illuminators (DVB-T/T2,
+    DAB, LTE, 5G): prc_batch_xambg of include/prcore.h, DESIGN.md section 28.  Batch j = 0 .. freqBins - 1 is the ``batchLen``
+    (1024 or 4096) samples from ``start + j hop`` of both channels (``hop`` None: batchLen); each surveillance batch is
+    correlated with its reference batch through their spectra -- ``filter="matched"`` multiplies by conj(R), as fast_xambg
+    does; ``"reciprocal"`` divides by R, with |R|^2 held above ``floor``^2 times the batch's energy --, lags 0 .. rangeBins are
+    kept, and a transform over the batches (freqBins: 256, 512, 1024, 2048 or 4096) gives the Doppler axis.  No wrap and no
+    zero padding: the last batch must end inside the channels.
+
+    The reciprocal filter turns every echo into one clean impulse per batch, so the data-dependent pedestal that a matched
+    filter leaves on a noise-like illuminator (about 1 / sqrt(B T) of every strong echo's peak) is not there: with batches
+    aligned to the useful parts of the symbols -- ``start = ofdm_symbol_start(ref, nfft, cp) + cp``, ``hop = nfft + cp``,
+    ``batchLen = nfft`` -- an echo ``a ref(t - d)``, d <= cp, peaks at ``a freqBins (occupied carriers / batchLen)``.
+    Two limits: on constant-modulus carriers (QPSK) the two filters coincide up to scale, and with batches that are not
+    aligned to the symbols the reciprocal filter is no better than the matched one.  A Doppler shift also rotates the
+    carriers inside a batch: echoes lose sinc(f_d batchLen / Fs) and leak between carriers, as in every batches algorithm.
+
+    Channels are 1-D (returns (freqBins, rangeBins + 1, 1), so it drops in where fast_xambg stood) or [nframes, n] stacks
+    (returns (nframes, freqBins, rangeBins + 1)), NumPy arrays or torch device tensors (zero copy, torch's current stream).
+    Column k is delay rangeBins - k, rows are mirrored and fftshift-ed as fast_xambg's; scene.expected_peak_cell holds with
+    the CPI taken as freqBins hop samples.  ``window``: a name or tuple for scipy's get_window over the freqBins batches, or an
+    array of freqBins values (slow-time taper)."""
+    if tuple(refChannel.shape) != tuple(srvChannel.shape):
+        raise ValueError("Input vectors must have the same length")
+    shape = residence.shape(refChannel)
+    if len(shape) not in (1, 2):
+        raise ValueError("batch_xambg takes one-dimensional channels or [nframes, n] stacks")
+    if filter not in _lib.BATCH_FILTERS:
+        raise ValueError(f"filter is 'reciprocal' or 'matched', not {filter!r}")
+    n, nframes = int(shape[-1]), (1 if len(shape) == 1 else int(shape[0]))
+    L, R, F = int(batchLen), int(rangeBins), int(freqBins)
+    hop, start, floor = (L if hop is None else int(hop)), int(start), float(floor)
+    if L not in _lib.BATCH_LENGTHS:
+        raise NotImplementedError(f"batch_xambg: batchLen = {L}: batches of {' or '.join(map(str, _lib.BATCH_LENGTHS))} samples")
+    if F not in _lib.BATCH_FREQ_BINS:
+        raise NotImplementedError(f"batch_xambg: freqBins = {F}: one of {', '.join(map(str, _lib.BATCH_FREQ_BINS))}")
+    if start < 0 or hop < 1:
+        raise ValueError(f"batch_xambg: start = {start} and hop = {hop}: start >= 0 and hop >= 1")
+    if not 0 <= R < L:
+        raise ValueError(f"batch_xambg: rangeBins = {R}: not in 0 .. batchLen - 1 = {L - 1}")
+    if start + (F - 1) * hop + L > n:
+        raise ValueError(f"batch_xambg: the last batch ends at start + (freqBins - 1) hop + batchLen = {start + (F - 1) * hop + L}, "
+                         f"beyond the {n} samples of a channel")
+    if not (floor >= 0.0 and np.isfinite(floor)):
+        raise ValueError(f"batch_xambg: floor = {floor}: a finite number >= 0")
+    if isinstance(window, (tuple, str)):
+        window = _named_window(window, F)
+    if window is not None and tuple(residence.shape(window)) != (F,):
+        raise ValueError(f"operands could not be broadcast together with shapes ({F},) {tuple(residence.shape(window))}")
+    side = residence.of(refChannel, srvChannel, mixed="the channels are both NumPy arrays or both device tensors")
+    if window is not None and _lib.is_device_tensor(window) and not side.torch:
+        raise ValueError("a device-tensor window goes with device-tensor channels")
+    desc = engine.batch_xambg_desc(n, L, R, F, hop, start, _lib.BATCH_FILTERS[filter], floor)
+    nws = engine.batch_xambg_workspace_bytes(desc, nframes)      # the library's own checks, still on the host
+    oshape = (F, R + 1, 1) if len(shape) == 1 else (nframes, F, R + 1)
+    if nframes == 0:
+        return side.nothing(oshape, np.complex64)
+    with side.device():
+        ref = side.put("bx_ref", refChannel, np.complex64)
+        srv = side.put("bx_srv", srvChannel, np.complex64)
+        win = None if window is None else side.put("bx_win", window, np.float32)
+        out = side.empty("bx_out", oshape, np.complex64)
+        ws = side.scratch("bx_ws", nws)
+        engine.batch_xambg_execute(desc, ref, srv, n, win, out, nframes, ws, side.stream)
+    return side.result(out, oshape, np.complex64)
+
+
+def ofdm_symbol_start(ref, nfft, cp, nsym=None, return_metric=False):
+    """Where the OFDM symbols of ``ref`` start, modulo nfft + cp, from the cyclic prefix (prc_ofdm_timing): for every offset
+    o = 0 .. nfft + cp - 1 the correlation of the ``cp`` samples from ``o + s (nfft + cp)`` with the samples ``nfft`` later is
+    summed over ``nsym`` symbols (float64 sums of the float32 products) and the offset of the largest magnitude is returned,
+    the lowest on ties.  The batches of ``batch_xambg`` are aligned with ``start = ofdm_symbol_start(...) + cp``,
+    ``hop = nfft + cp``, ``batchLen = nfft``.  ``nsym`` None: as many symbols as the length allows, 4096 at most.
+    ``ref`` is a 1-D NumPy array or torch device tensor; returns a Python int -- one small device-to-host copy -- and, with
+    ``return_metric``, the float64 metric [nfft + cp] beside it (an array, or a tensor on the caller's device)."""
+    shape = residence.shape(ref)
+    if len(shape) != 1:
+        raise ValueError("ofdm_symbol_start takes a one-dimensional channel")
+    n, nfft, cp = int(shape[0]), int(nfft), int(cp)
+    if nfft < 2 or not 1 <= cp < nfft:
+        raise ValueError(f"ofdm_symbol_start: nfft = {nfft}, cp = {cp}: nfft >= 2 and 1 <= cp < nfft")
+    sym = nfft + cp
+    most = (n - nfft) // sym - 1
+    nsym = min(most, 4096) if nsym is None else int(nsym)
+    if nsym < 1 or nsym > most:
+        raise ValueError(f"ofdm_symbol_start: (nsym + 1) (nfft + cp) + nfft = {(max(nsym, 1) + 1) * sym + nfft} samples are needed, "
+                         f"the channel has {n}")
+    side = residence.of(ref)
+    with side.device():
+        x = side.put("ot_ref", ref, np.complex64)
+        metric = side.empty("ot_metric", (sym,), np.float64)
+        where = side.empty("ot_start", (1,), np.int32)
+        engine.ofdm_timing(x, n, nfft, cp, nsym, metric, where, side.stream)
+        at = int(side.fetch(where, (1,), np.int32)[0])
+    return (at, side.result(metric, (sym,), np.float64)) if return_metric else at

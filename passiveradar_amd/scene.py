@@ -128,6 +128,28 @@ def make_ofdm_scene(n, sample_rate, rangeBins, seed, nfft=256, guard=0.25, ref_n
     return ref, _echo_channel(ref, _cwhite(gen, n), sample_rate, rangeBins, **kw)
 
 
+def make_qam_ofdm_scene(n, sample_rate, rangeBins, seed, nfft=1024, cp=128, guard=0.25, order=8, symbol_start=0, ref_noise_db=-60.0,
+                        **kw):
+    """Scene on a QAM-OFDM illuminator (DVB-T/T2, LTE style) with its symbol structure intact: ``nfft``-point symbols, each
+    behind a cyclic prefix of ``cp`` samples, square QAM of ``order`` levels per axis (8: 64-QAM; 2: QPSK) on the carriers
+    |f| <= 0.5 (1 - guard) and nothing on the others.  Unlike make_ofdm_scene no brick-wall mask runs over the whole block: a
+    mask would smear every symbol into its neighbours, and the per-symbol spectrum is what a reciprocal filter divides by
+    (range_doppler_processing.batch_xambg).  The stream is rolled by ``symbol_start`` samples (symbol s then starts at
+    symbol_start + s (nfft + cp); the useful part cp later), normalised to unit power, and white reference-channel noise
+    ``ref_noise_db`` below it is added.  complex64; echoes as in make_fm_scene."""
+    gen = np.random.Generator(np.random.Philox(key=seed))
+    sym = nfft + cp
+    nsym = -(-n // sym)
+    levels = np.arange(-(order - 1), order, 2)
+    qam = gen.choice(levels, (nsym, nfft)) + 1j * gen.choice(levels, (nsym, nfft))
+    used = np.abs(np.fft.fftfreq(nfft)) <= 0.5 * (1.0 - guard)
+    body = np.fft.ifft(qam * used, axis=1)
+    x = np.roll(np.concatenate([body[:, nfft - cp:], body], axis=1).reshape(-1)[:n], symbol_start)
+    x /= np.sqrt(np.mean(np.abs(x) ** 2))
+    ref = (x + 10.0 ** (ref_noise_db / 20.0) * _cwhite(gen, n)).astype(np.complex64)
+    return ref, _echo_channel(ref, _cwhite(gen, n), sample_rate, rangeBins, **kw)
+
+
 def make_ar2_scene(n, sample_rate, rangeBins, seed, radius=0.99, pole_freq=0.1, **kw):
     """Scene on an AR(2) illuminator: complex white noise through 1 / (1 - 2 r cos(w) z^-1 + r^2 z^-2), poles at
     r e^{+-j w} (w = 2 pi ``pole_freq`` cycles per sample), applied circularly in the frequency domain (stationary
